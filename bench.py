@@ -1,25 +1,33 @@
 #!/usr/bin/env python3
-"""Headline benchmark: embedding-update sweeps/sec + achieved HBM GB/s of the K3 SpMM kernel.
+"""Headline benchmark: embedding-update sweeps/sec (with --full also the achieved HBM GB/s of the K3 SpMM kernel).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--workload rmat2m|uniform2m|rmat200k|powerlaw10m|tiny]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one Jacobi sweep  Z <- X + gamma * P Z  over the whole graph, P frozen: the K3
 kernels, the deterministic L1-delta reduction, the host read-back of that scalar (the
 reference decides after every sweep, embedder.py:94-105) and, for N > 1, the all-reduce of that
 scalar.  Inputs are resident in HBM before the timed region.
 
-Timing protocol: W warm-up sweeps, then B blocks (default 5) of EXACTLY K sweeps, each block bracketed
-by a barrier + torch.cuda.synchronize() on both sides (host clock, MAX over ranks) and by a HIP event pair on the
-sweep's stream; `value` / `ms_per_step` are the MEDIAN block, `ms_per_step_min` / `_max` the spread.
+Timing protocol: W warm-up sweeps, then B blocks of EXACTLY K sweeps, each block bracketed by a barrier +
+torch.cuda.synchronize() on both sides (host clock, MAX over ranks) and by a HIP event pair on the sweep's stream;
+`value` / `ms_per_step` are the MEDIAN block, `ms_per_step_min` / `_max` the spread.  B defaults to 1, so that a plain
+run times exactly K sweeps; with --full to 5.
+
+A plain run does only what the headline needs: input, engine, build_P, warm-up, the timed sweeps, `--dump-outputs`
+if given, the JSON line.  `--full` adds everything else this script measures or checks: build_P's own times, the
+first sweep and P against the C oracle, the CPU baselines, the roofline of the K3 kernels (HIP events per kernel in
+the timed blocks), the further workloads of `--legs`, and at N > 1 the fabric probe, the `comm` block, the delta-stream
+A/B and the divisions of `--also-exchange`.
 
 N > 1: one process per GPU over RCCL.  `python bench.py --gpus N` starts the N ranks itself (fresh child
 processes through torch.distributed.run, before this process has touched a GPU) and relays rank 0's JSON
 line; started under torchrun (WORLD_SIZE set) it is one of the ranks.  The graph is fixed and divided, so
 scaling is STRONG: by default every GPU sweeps d/N columns of all rows (no exchange per sweep);
 `--exchange allgather_all` is north_star's literal plan (rows divided, one in-place RCCL all-gather of the
-updated rows per sweep), `halo` / `halo_p2p` / `allgather` are the leaner row splits.  At N > 1 the record also
-carries a `comm` block (what RCCL saw, time inside the collectives, the delta-stream variant timed beside the default)
-and -- `--also-exchange`, default allgather_all,allgather -- the same measurement of north_star's literal division
+updated rows per sweep), `halo` / `halo_p2p` / `allgather` are the leaner row splits.  With --full, at N > 1 the
+record also carries a `comm` block (what RCCL saw, time inside the collectives, the delta-stream variant timed beside
+the default) and -- `--also-exchange`, default allgather_all,allgather -- the same measurement of north_star's literal division
 in `north_star_literal` and of the live-rows all-gather in `other_divisions`, so ONE record answers both "what
 scales" and "what north_star asked for".  `--rehearse-rccl` runs that whole N > 1 flow through the real RCCL
 library with the one rank a one-GPU box can give it.  Rank 0 prints one JSON line.
@@ -54,9 +62,17 @@ def make_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of --steps sweeps each (SURVEY 8d: median of 5); the JSON line reports the median "
-                         "block and the spread")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps sweeps each; the JSON line reports the median block and the spread "
+                         "(default: 1, with --full 5 -- SURVEY 8d: median of 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also everything else: build_P timed, parity against the C oracle, CPU "
+                         "baselines, roofline, the --legs workloads; at N > 1 the fabric probe, comm block, delta-stream "
+                         "A/B and --also-exchange divisions (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps write what the last one computed as DIR/<name>.npy: delta (float64), "
+                         "Z (float32, float64 for f64 inputs; whole up to 48 MB, else a fixed seeded sample of rows) "
+                         "and Z_rows (the rows written, as float64)")
     ap.add_argument("--workload", default="rmat2m", choices=sorted(WORKLOADS))
     ap.add_argument("--gamma", type=float, default=0.76)
     ap.add_argument("--chunks", type=int, default=None)
@@ -77,8 +93,9 @@ def make_parser():
                          "the same for the live rows only; halo / halo_p2p = rows sent only to the ranks that read "
                          "them (clane_amd/halo.py, partition.py; DESIGN.md section 6)")
     ap.add_argument("--also-exchange", default="allgather_all,allgather",
-                    help="N > 1: after the main division's timed blocks, rebuild the engine with each of these divisions "
-                         "(comma-separated) and report its sweeps/s, parity and collective time in the same record: "
+                    help="N > 1, with --full: after the main division's timed blocks, rebuild the engine with each of "
+                         "these divisions (comma-separated) and report its sweeps/s, parity and collective time in the "
+                         "same record: "
                          "allgather_all = north_star's row partition + one all-gather of the owned rows per sweep -> "
                          "`north_star_literal`; the others (allgather = the same for the rows that change and are read; "
                          "halo, halo_p2p) -> `other_divisions`.  The main division is skipped; none = off.  The default "
@@ -93,10 +110,11 @@ def make_parser():
                          "collective is the identity on one rank).  Shows no scaling; catches API, dtype and stream "
                          "mistakes that the gloo rehearsals cannot.  Not a headline number.")
     ap.add_argument("--no-fabric-probe", action="store_true",
-                    help="N > 1: skip tools/fabric_probe.py (child processes that time the all-gather / direct exchange of "
-                         "a rank's slice of Z and log RCCL's algorithm / protocol / channels before the timed run)")
+                    help="N > 1, with --full: skip tools/fabric_probe.py (child processes that time the all-gather / "
+                         "direct exchange of a rank's slice of Z and log RCCL's algorithm / protocol / channels before the timed run)")
     ap.add_argument("--no-delta-stream-ab", action="store_true",
-                    help="N > 1: skip the extra timed blocks with the delta's all-reduce on its own stream (comm.delta_stream_ab)")
+                    help="N > 1, with --full: skip the extra timed blocks with the delta's all-reduce on its own stream "
+                         "(comm.delta_stream_ab)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses cuda:0 (RCCL refuses that: use --backend gloo)")
     ap.add_argument("--host-sync", default="auto", choices=["auto", "every-sweep", "pipelined"],
@@ -111,16 +129,19 @@ def make_parser():
                     help="after the timed sweeps also run the WHOLE algorithm from Z = X -- Embedder.iterate() to "
                          "tolerance (build_P + propagate per outer round) -- and report rounds, sweeps, wall time")
     ap.add_argument("--tolerence", type=int, default=10, help="(reference spelling) for --iterate")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (the parity check stays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines (the parity check stays)")
     ap.add_argument("--legs", default="auto",
-                    help="further workloads measured after the main one, in the same process and JSON line (one GPU only): "
+                    help="with --full: further workloads measured after the main one, in the same process and JSON line "
+                         "(one GPU only): "
                          "auto (default) = uniform2m,rmat200k,powerlaw10m when the main workload is the headline (rmat2m): the "
                          "roofline's no-reuse anchor -> roofline.anchor, BASELINE configs 2 and 4 (the latter incl. "
                          "Embedder.iterate() to tolerence) -> other_workloads; a comma-separated list; none = off")
     ap.add_argument("--budget-s", type=float, default=270.0,
                     help="wall-time plan of the whole command: a leg is only started while the time used so far plus its "
                          "estimate fits (the driver allows 600 s; the main record never waits for a leg)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the first-sweep check against the C oracle too")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the first-sweep check against the C oracle too")
     ap.add_argument("--column-slice-of", type=int, default=None, metavar="N",
                     help="one-GPU rehearsal of ONE rank of the N-GPU column split: sweep only the first d/N columns "
                          "(what every rank of `--gpus N` does); for profiling that rank's kernels, not a headline number")
@@ -135,6 +156,8 @@ def main():
                                                                      "allgather", "allgather_all")]
     if unknown:
         raise SystemExit(f"--also-exchange: unknown division(s) {unknown}")
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:        # no launcher: be the launcher
         raise SystemExit(launch_ranks(args.gpus))
     if os.environ.get("CLANE_BENCH_WATCHDOG_S"):                # debugging aid: every rank dumps its stack every S seconds
@@ -142,8 +165,9 @@ def main():
         faulthandler.dump_traceback_later(float(os.environ["CLANE_BENCH_WATCHDOG_S"]), repeat=True, file=sys.stderr)
 
     import torch.distributed as dist
-    n_also = 0 if args.also_exchange == "none" else len([x for x in args.also_exchange.split(",") if x])
-    plan = {"driver_limit_s": DRIVER_LIMIT_S, "fabric_probe_s_at_most": 120.0 if args.gpus > 1 and not args.no_fabric_probe else 0.0,
+    n_also = 0 if (args.also_exchange == "none" or not args.full) else len([x for x in args.also_exchange.split(",") if x])
+    probe = args.full and args.gpus > 1 and not args.no_fabric_probe
+    plan = {"driver_limit_s": DRIVER_LIMIT_S, "fabric_probe_s_at_most": 120.0 if probe else 0.0,
             "generation_and_main_division_s_estimate": 60.0, "divisions_after_the_main_one": n_also if args.gpus > 1 else 0}
     # every division after the main one gets the same share of what the driver's limit leaves (at most LITERAL_DEADLINE_S)
     division_deadline = min(LITERAL_DEADLINE_S, (DRIVER_LIMIT_S - 30.0 - plan["fabric_probe_s_at_most"]
@@ -165,15 +189,22 @@ def main():
         f"generated in {time.perf_counter() - t0:.1f}s")
 
     t0 = time.perf_counter()
-    m = measure_division(args, ranks, csr, X, args.exchange, time_kernels=True)
+    m = measure_division(args, ranks, csr, X, args.exchange, time_kernels=args.full, outputs=bool(args.dump_outputs))
     TIMELINE["main_division_s"] = time.perf_counter() - t0
     eng = m["eng"]
     result = main_record(args, ranks, m, X, E)
     if ranks.grouped:
         result["time_plan"] = dict(plan, spent_s=TIMELINE)
+    if args.dump_outputs:
+        outputs = m.pop("outputs")
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
+        del outputs
 
     Z1_oracle, failed = None, False
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         Z1_oracle, failed = check_parity(args, ranks, eng, m, csr, X, result)
         if failed:                  # every rank leaves, non-zero, together
             if rank == 0:
@@ -182,7 +213,8 @@ def main():
                 dist.destroy_process_group()
             raise SystemExit(f"parity check failed: {result.get('parity_rel_l2_vs_oracle_after_1_sweep')} "
                              f"(P: {result.get('parity_P_rel_l2_vs_oracle')})")
-    if not args.no_parity and not ranks.grouped and not args.column_slice_of and WORKLOADS[args.workload][4] != "f64":
+    if args.full and not args.no_parity and not ranks.grouped and not args.column_slice_of and \
+            WORKLOADS[args.workload][4] != "f64":
         if per_edge_parity(args, ranks, eng, csr, X, result):
             print(json.dumps(result), flush=True)
             raise SystemExit(f"per-edge parity check of P failed: {result['parity_P_per_edge_rel_l2_vs_oracle']}")
@@ -190,7 +222,7 @@ def main():
         result["iterate"] = run_iterate(args, ranks, eng, csr, X)
 
     # ---- further workloads in the same record (one GPU): the roofline's anchor, BASELINE configs 2 and 4 --------
-    legs = [] if (ranks.grouped or args.column_slice_of or args.legs == "none") else \
+    legs = [] if (not args.full or ranks.grouped or args.column_slice_of or args.legs == "none") else \
         (list(LEG_SETTINGS) if args.workload == "rmat2m" else []) if args.legs == "auto" else \
         [x for x in args.legs.split(",") if x]
     if legs:
@@ -238,7 +270,7 @@ def main():
                 if rank == 0:
                     print(json.dumps(dict(result, **(extra or {}))), flush=True)
 
-    also = [] if (args.also_exchange == "none" or not ranks.grouped or args.column_slice_of) else \
+    also = [] if (not args.full or args.also_exchange == "none" or not ranks.grouped or args.column_slice_of) else \
         [x for x in args.also_exchange.split(",") if x and x != eng.exchange
          and not (ranks.rehearsal and x not in ("columns", "allgather", "allgather_all"))]   # what ONE rank can be made to issue
     if also:

@@ -4,6 +4,7 @@ from __future__ import annotations
 import statistics
 import time
 
+import numpy as np
 import torch
 
 from .common import log
@@ -67,9 +68,27 @@ def delta_stream_ab(eng, args, ranks: Ranks, pipelined: bool, off_wall) -> dict:
         eng.use_delta_stream(False)
 
 
-def measure_division(args, ranks: Ranks, csr, X, exchange: str, time_kernels: bool):
-    """Engine for `exchange`, build_P (timed on its second call), the parity sweep, warm-up, and the timed blocks.
-    Returns a dict of everything measured (every rank gets the same numbers where they are reduced)."""
+OUTPUT_BYTES = 48 << 20      # --dump-outputs: Z is written whole up to this size, else a fixed seeded sample of its rows
+
+
+def last_step_outputs(eng, delta: float) -> dict:
+    """What a caller of the timed path holds after its last sweep: the L1 delta that sweep returned and the embeddings
+    Z (get_Z: vertex order; collective when N > 1).  Z larger than OUTPUT_BYTES is sampled by rows (a fixed seed, so
+    two runs with the same arguments write the same rows); `Z_rows` names them."""
+    Z = eng.get_Z()
+    Z = Z if Z.dtype == torch.float64 else Z.float()
+    V, d = Z.shape
+    n = max(1, min(V, OUTPUT_BYTES // max(1, d * Z.element_size())))
+    rows = np.arange(V) if n == V else np.sort(np.random.default_rng(0).choice(V, size=n, replace=False))
+    return {"Z": Z[torch.from_numpy(rows)].numpy(), "Z_rows": rows.astype(np.float64),
+            "delta": np.array([delta], dtype=np.float64)}
+
+
+def measure_division(args, ranks: Ranks, csr, X, exchange: str, time_kernels: bool, outputs: bool = False):
+    """Engine for `exchange`, build_P, warm-up, and the timed blocks; with --full also build_P timed (on its second
+    and third calls) and the parity sweep before the warm-up.  `outputs`: keep last_step_outputs() of the last timed
+    sweep as out["outputs"].  Returns a dict of everything measured (every rank gets the same numbers where they are
+    reduced)."""
     from clane_amd.embedder import Embedder
     from clane_amd.engine import SweepEngine
     world, rank, dev = ranks.world, ranks.rank, ranks.dev
@@ -91,12 +110,12 @@ def measure_division(args, ranks: Ranks, csr, X, exchange: str, time_kernels: bo
         f"class={sum(0 if l is None else l[0].numel() for l in eng.class_rows)} "
         f"thresholds {eng.long_threshold}/{eng.hub_threshold}")
 
-    # build_P (timed separately, not part of a step), P frozen afterwards.  Twice: "cold" = the row norms recomputed by
-    # K0 (a pass over Z: the first build_P of a run, or after set_Z), and as it runs in every later outer round of
-    # Embedder.iterate(), where the outer-delta pass (embedder.py:60) has left the norms behind.
+    # build_P (timed separately, not part of a step), P frozen afterwards.  With --full twice more: "cold" = the row
+    # norms recomputed by K0 (a pass over Z: the first build_P of a run, or after set_Z), and as it runs in every later
+    # outer round of Embedder.iterate(), where the outer-delta pass (embedder.py:60) has left the norms behind.
     eng.build_P()                      # first call loads the code objects
-    times = {}
-    for name, cold in (("cold", True), ("in_loop", False)):
+    times = {"in_loop": None, "cold": None}
+    for name, cold in (("cold", True), ("in_loop", False)) if args.full else ():
         if cold:
             eng.sq_ok[eng.cur] = False
         ranks.barrier()
@@ -109,7 +128,7 @@ def measure_division(args, ranks: Ranks, csr, X, exchange: str, time_kernels: bo
     if args.calibrate:      # known-size streaming read in this library's own 16 B/lane access pattern
         eng.l1_between(0, 1)
         out["calibration_bytes"] = 2 * eng.part.n_local * eng.ld * eng.Zcur.element_size()    # l1_distance reads two matrices
-    if not args.no_parity:              # the sweep the oracle is checked against (Z = X before it); collective
+    if args.full and not args.no_parity:    # the sweep the oracle is checked against (Z = X before it); collective
         eng.sweep(args.gamma)
         Z1 = eng.get_Z()
         out["Z1"] = Z1 if rank == 0 else None
@@ -123,11 +142,14 @@ def measure_division(args, ranks: Ranks, csr, X, exchange: str, time_kernels: bo
     out["pipelined"], out["host_sync"] = pipelined, host_sync
     eng.time_kernels = time_kernels
     eng.kernel_events = []
-    eng.time_collectives = ranks.grouped
+    eng.time_collectives = ranks.grouped and args.full
     eng.collective_events = []
     wall, local_wall, hip_ms, delta = timed_blocks(eng, args, ranks, pipelined, max(1, args.blocks))
     eng.time_kernels = eng.time_collectives = False
-    ab = delta_stream_ab(eng, args, ranks, pipelined, wall) if (ranks.grouped and not args.no_delta_stream_ab) else None
+    if outputs:                         # before anything below sweeps again
+        out["outputs"] = last_step_outputs(eng, delta)
+    ab = delta_stream_ab(eng, args, ranks, pipelined, wall) if (
+        ranks.grouped and args.full and not args.no_delta_stream_ab) else None
     med = statistics.median(wall)
     out.update({
         "delta": delta, "elapsed": med, "value": args.steps / med, "ms_per_step": med / args.steps * 1e3,

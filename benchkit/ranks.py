@@ -128,7 +128,7 @@ def start_ranks(args) -> Ranks:
     if world > 1:       # torchrun starts every rank with OMP_NUM_THREADS=1: give each rank its share of the host cores
         torch.set_num_threads(max(1, (os.cpu_count() or 1) // world))
     probe = None
-    if (world > 1 or args.rehearse_rccl) and not args.no_fabric_probe:
+    if (world > 1 or args.rehearse_rccl) and args.full and not args.no_fabric_probe:
         # BEFORE this process touches its GPU: child processes measure what RCCL and the links do with the literal
         # plan's message (this rank's slice of Z) and log RCCL's choices; the timed run below never logs
         import importlib.util

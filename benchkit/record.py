@@ -154,7 +154,8 @@ def roofline_block(args, world, m) -> dict:
 
 
 def main_record(args, ranks: Ranks, m, X, E) -> dict:
-    """The JSON line of the main division (the driver's contract + roofline; parity and baselines are added later)."""
+    """The JSON line of the main division (the driver's contract; with --full also the roofline, build_P's times and
+    the comm block -- parity and baselines are added later)."""
     gen, V, _, d, dname, gseed, xseed = WORKLOADS[args.workload]
     eng, world = m["eng"], ranks.world
     result = {
@@ -173,17 +174,19 @@ def main_record(args, ranks: Ranks, m, X, E) -> dict:
                    "parallelism": describe_parallelism(args, world, eng, X, E),
                    "host_sync": (f"pipelined ({m['host_sync']}): the delta of sweep t is read while sweep t+1 runs"
                                  if m["pipelined"] else f"after every sweep ({m['host_sync']}; the reference's order)")},
-        "roofline": roofline_block(args, world, m),
-        "build_P_ms": m["build_P_ms"], "build_P_cold_ms": m["build_P_cold_ms"],
-        "build_P_note": "build_P_ms: as in every outer round of Embedder.iterate() after the first -- the row norms "
-                        "(similarity.py:37) are left behind by the pass that measures the round's outer delta "
-                        "(embedder.py:60), which reads every row of the new Z anyway; build_P_cold_ms: the norms "
-                        "recomputed by row_sqnorm first (the first round, or after set_Z)",
         "last_delta": m["delta"],
     }
+    if args.full:
+        result.update({
+            "roofline": roofline_block(args, world, m),
+            "build_P_ms": m["build_P_ms"], "build_P_cold_ms": m["build_P_cold_ms"],
+            "build_P_note": "build_P_ms: as in every outer round of Embedder.iterate() after the first -- the row norms "
+                            "(similarity.py:37) are left behind by the pass that measures the round's outer delta "
+                            "(embedder.py:60), which reads every row of the new Z anyway; build_P_cold_ms: the norms "
+                            "recomputed by row_sqnorm first (the first round, or after set_Z)"})
     if m["calibration_bytes"] is not None:
         result["calibration"] = {"kernel": "l1_distance_kernel", "bytes_read": m["calibration_bytes"]}
-    if ranks.grouped:
+    if ranks.grouped and args.full:
         result["comm"] = comm_block(args, ranks, m)
     if ranks.rehearsal:
         result["rehearsal"] = ("ONE rank in a real RCCL group with every collective issued (--rehearse-rccl): the N > 1 "

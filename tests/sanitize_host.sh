@@ -18,4 +18,8 @@ ASAN_OPTIONS=detect_leaks=1 "$out/sanitize_host" "$out/data"
 gcc -c -O1 -g -fopenmp oracle/clane_oracle.c -o "$out/oracle_plain.o"
 $CXX -fopenmp -fsanitize=thread tests/sanitize_host_main.cpp clane_amd/csrc/host_loader.cpp "$out/oracle_plain.o" \
     -o "$out/sanitize_host_tsan"
-"$out/sanitize_host_tsan" "$out/data" loader-only
+# ThreadSanitizer's shadow layout expects the binary where a kernel with the usual ASLR entropy puts it; on hosts with
+# more entropy it dies with "unexpected memory mapping".  Run it with this process's address randomisation off.
+norand=()
+if setarch "$(uname -m)" -R true 2>/dev/null; then norand=(setarch "$(uname -m)" -R); fi
+"${norand[@]}" "$out/sanitize_host_tsan" "$out/data" loader-only

@@ -1187,6 +1187,49 @@ def test_config2_full_iterate_vs_c_oracle(tmp_path):
     assert tol <= len(emb.sweep_counts) <= 40 and tol <= len(sweeps_or) <= 40
 
 
+def test_bench_plain_run_times_steps_and_dumps_the_last_sweep(tmp_path, dev):
+    """A plain `bench.py` run (no --full) times exactly --steps sweeps in one block and carries only the headline; with
+    --dump-outputs it writes what the last timed sweep computed -- the same files on a second run with the same
+    arguments, and the C oracle's Z and delta after warm-up + steps sweeps from Z = X."""
+    import json
+    import subprocess
+    import sys
+    from benchkit.common import WORKLOADS
+    root = Path(__file__).resolve().parent.parent
+    steps, warmup = 3, 2
+    recs = []
+    for run in ("a", "b"):
+        got = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps",
+                              str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert got.returncode == 0, got.stderr[-2000:]
+        lines = [ln for ln in got.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    r = recs[0]
+    assert r["steps"] == steps and r["warmup"] == warmup and r["blocks"] == 1 and len(r["block_ms_per_step"]) == 1
+    assert r["ms_per_step"] > 0 and r["value"] == pytest.approx(1e3 / r["ms_per_step"]) and r["dtype"] == "f32"
+    assert r["unit"] == "sweeps/s" and r["higher_is_better"] is True
+    for moved in ("roofline", "build_P_ms", "parity_rel_l2_vs_oracle_after_1_sweep", "cpu_baseline", "other_workloads"):
+        assert moved not in r
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("Z", "Z_rows", "delta")}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("Z", "Z_rows", "delta")}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["Z"].dtype == np.float32 and a["Z_rows"].dtype == a["delta"].dtype == np.float64
+    assert all(np.array_equal(a[n], b[n]) for n in a)                # deterministic kernels, same seeded input
+    assert float(a["delta"][0]) == r["last_delta"]
+    _, V, E, d, _, gseed, xseed = WORKLOADS["tiny"]
+    csr = synth.rmat_csr(V, E, seed=gseed, device=str(dev))           # the generator bench.py runs
+    X = synth.gaussian_X(V, d, seed=xseed).float()
+    P, _ = OC.build_P(csr.rowptr, csr.colidx, X)
+    Z = X
+    for _ in range(warmup + steps):
+        Z, delta = OC.sweep(csr.rowptr, csr.colidx, P, X, Z, 0.76)
+    rows = torch.from_numpy(a["Z_rows"].astype(np.int64))
+    assert a["Z"].shape == (len(rows), d) and O.rel_l2(torch.from_numpy(a["Z"]), Z[rows]) < 1e-5
+    assert float(a["delta"][0]) == pytest.approx(float(delta), rel=1e-4)
+
+
 def test_bench_two_processes_on_one_gpu_match_one_process(tmp_path):
     """bench.py's N > 1 flow end to end -- torchrun, process group, input checksum, column-split engine,
     collectives on device tensors, barrier + MAX timing, one JSON line from rank 0 -- with two real processes
@@ -1201,7 +1244,7 @@ def test_bench_two_processes_on_one_gpu_match_one_process(tmp_path):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    common = ["--workload", "tiny", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-fabric-probe"]
+    common = ["--workload", "tiny", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-fabric-probe", "--full"]
     one = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1"] + common, capture_output=True,
                          text=True, timeout=600, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -1275,7 +1318,8 @@ def test_bench_north_star_row_partition_two_processes(tmp_path):
     two = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
                           "--exchange", "allgather_all", "--also-exchange", "allgather", "--workload", "tiny", "--steps", "4",
                           "--warmup", "2", "--blocks", "2", "--no-cpu-baseline", "--host-sync", "every-sweep",
-                          "--no-delta-stream-ab", "--no-fabric-probe"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+                          "--no-delta-stream-ab", "--no-fabric-probe", "--full"], capture_output=True, text=True, timeout=600,
+                         cwd=root, env=env)
     assert two.returncode == 0, two.stderr[-2000:]
     r2 = json.loads([ln for ln in two.stdout.splitlines() if ln.startswith("{")][-1])
     assert "exchange=allgather_all over RCCL per chunk" in r2["config"]["parallelism"] and r2["n_gpus"] == 2

@@ -640,7 +640,7 @@ def test_bench_four_ranks_share_one_gpu_with_an_idle_column_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     run = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--backend", "gloo", "--share-gpu",
                           "--workload", "tiny12", "--exchange", "columns", "--steps", "3", "--warmup", "1", "--blocks",
-                          "3", "--also-exchange", "allgather_all,allgather,halo"],
+                          "3", "--also-exchange", "allgather_all,allgather,halo", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -717,7 +717,8 @@ def test_bench_main_record_survives_a_stuck_literal_block():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["CLANE_BENCH_LITERAL_DEADLINE_S"] = "0.001"
     run = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-                          "--workload", "tiny", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-fabric-probe"],
+                          "--workload", "tiny", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-fabric-probe",
+                          "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert run.returncode != 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -740,7 +741,7 @@ def test_bench_n_gpu_flow_through_real_rccl_with_one_rank():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--workload", "tiny", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline"]
+    common = ["--workload", "tiny", "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-cpu-baseline", "--full"]
     plain = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common, capture_output=True, text=True, timeout=600,
                            cwd=ROOT, env=env)
     assert plain.returncode == 0, plain.stderr[-2000:]

@@ -29,7 +29,9 @@ def test_g1_cosine_known_answers():
     assert O.cosine_similarity(torch.tensor([0.0, 1.0]), torch.tensor([1.0, 0.0])).numpy() == pytest.approx(g["orth"], abs=1e-7)
     assert O.cosine_similarity(v, -v).numpy() == pytest.approx(g["opp"], abs=1e-6)
     out = O.cosine_similarity(torch.from_numpy(g["a4"]), torch.from_numpy(g["b4"]))
-    np.testing.assert_array_equal(out.numpy(), g["out4"])          # same torch ops: bit-exact
+    # same torch ops, but the CPU kernels behind them (vector width, BLAS path) depend on the host, so their float32
+    # summation order may differ from the one the fixture was made on: within a few ulp (seen: 2), not bit-exact
+    np.testing.assert_array_max_ulp(out.numpy(), g["out4"], maxulp=4)
     out64 = O.cosine_similarity(torch.from_numpy(g["a64"]), torch.from_numpy(g["b64"]))
     assert out64.dtype == torch.float64
     np.testing.assert_array_equal(out64.numpy(), g["out64"])
