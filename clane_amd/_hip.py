@@ -20,7 +20,7 @@ import torch
 
 LIB_NAME = "libclane_hip.so"
 LIB_PATH = Path(__file__).resolve().parent / LIB_NAME
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 SCORE_REFERENCE, SCORE_PER_EDGE, SCORE_RAW_DOT = 0, 1, 2
 SPMM_SINKS_UNTOUCHED = 1
@@ -74,6 +74,12 @@ for _s in ("f32", "f64"):
     SIGNATURES[f"clane_edge_score_finalize_{_s}"] = (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p])
     SIGNATURES[f"clane_segment_softmax_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p])
     SIGNATURES[f"clane_pair_cosine_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p])
+    SIGNATURES[f"clane_edge_score_pair_{_s}"] = (
+        C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _i32, _i64, _p, _i64, _p])
+    SIGNATURES[f"clane_edge_score_class_pair_{_s}"] = (
+        C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _i32, _p, _p])
+for _s in ("f32", "f64", "bf16"):
+    SIGNATURES[f"clane_project_rows_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p])
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
 _ACC = {torch.float32: torch.float32, torch.float64: torch.float64, torch.bfloat16: torch.float32}
@@ -315,6 +321,23 @@ class KernelBackend(abc.ABC):
     def contiguous_matrix(self, shape, dtype, device): ...
     @abc.abstractmethod
     def open_shared_matrix(self, handle, shape, dtype, device): ...
+
+    # bilinear similarity (AsymmertricSimilarity): not abstract -- a backend without them still serves every other path,
+    # and SweepEngine.build_P_bilinear is the only caller
+    def project_rows(self, Z, d: int, W, Y):
+        """Y[:, :2d] = Z[:, :d] . W^T for every row of Z (W: [2d, d], accumulate dtype)."""
+        raise NotImplementedError(f"{type(self).__name__} has no project_rows")
+
+    def edge_score_pair(self, rowptr, colidx, nrows, row0, S, N, d, scores, long_threshold=0, long_rows=None,
+                        fuse_softmax=False):
+        """edge_score with two tables: the raw dot of S[row0 + r, :d] and N[col, :d]."""
+        raise NotImplementedError(f"{type(self).__name__} has no edge_score_pair")
+
+    def edge_score_class_pair(self, rowptr, colidx, item_e0, item_len, item_slot, item_row, items_per_block,
+                              class_rows, slot_ptr, row0, S, N, d, scores, stats=None, fuse_softmax=False,
+                              n_slots=None, row_parts=1):
+        """edge_score_class with two tables, as edge_score_pair."""
+        raise NotImplementedError(f"{type(self).__name__} has no edge_score_class_pair")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -571,6 +594,58 @@ class HipKernels(KernelBackend):
         dp, ldd = _mat(dst, "dst")
         self._invoke(self._fn("clane_gather_rows", src.dtype), "clane_gather_rows",
                      sp, lds, _vec(idx, torch.int32, "idx"), idx.numel(), d, dp, ldd, self._stream(src))
+
+    # -- bilinear similarity -------------------------------------------------------------
+    def project_rows(self, Z, d: int, W, Y):
+        """Y[r, :2d] = W . Z[r, :d] for every row r of Z (MFMA).  W: [2d, d] contiguous, Y: [rows(Z), >= 2d], both in
+        the accumulate dtype of Z."""
+        zp, ldz = _mat(Z, "Z")
+        yp, ldy = _mat(Y, "Y")
+        acc = acc_dtype(Z.dtype)
+        if tuple(W.shape) != (2 * d, d):
+            raise ValueError(f"project_rows: W must be [2d, d] = [{2 * d}, {d}], got {tuple(W.shape)}")
+        if Y.dtype != acc or Y.shape[0] < Z.shape[0]:
+            raise ValueError(f"project_rows: Y must be {acc} with at least {Z.shape[0]} rows")
+        self._check(self._fn("clane_project_rows", Z.dtype)(
+            zp, Z.shape[0], d, ldz, _vec(W, acc, "W"), yp, ldy, self._stream(Z)), "clane_project_rows")
+
+    def edge_score_pair(self, rowptr, colidx, nrows: int, row0: int, S, N, d: int, scores, long_threshold: int = 0,
+                        long_rows=None, fuse_softmax: bool = False):
+        """K1 with two tables: score of edge (r, c) = dot(S[row0 + r, :d], N[c, :d]) (S = Y[:, :d], N = Y[:, d:]
+        for the bilinear similarity); long rows and fused softmax as edge_score."""
+        sp, lds = _mat(S, "S")
+        np_, ldn = _mat(N, "N")
+        if S.dtype != N.dtype:
+            raise ValueError("edge_score_pair: S and N must share a dtype")
+        n_long = 0 if long_rows is None else long_rows.numel()
+        self._check(self._fn("clane_edge_score_pair", S.dtype)(
+            _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), nrows, row0, sp, lds, np_, ldn, d,
+            _vec(scores, S.dtype, "scores"), SCORE_FUSE_SOFTMAX if fuse_softmax else 0, long_threshold,
+            None if n_long == 0 else _vec(long_rows, torch.int32, "long_rows"), n_long,
+            self._stream(S)), "clane_edge_score_pair")
+
+    def edge_score_class_pair(self, rowptr, colidx, item_e0, item_len, item_slot, item_row, items_per_block: int,
+                              class_rows, slot_ptr, row0: int, S, N, d: int, scores, stats=None,
+                              fuse_softmax: bool = False, n_slots: Optional[int] = None, row_parts: int = 1):
+        """edge_score_class with two tables, as edge_score_pair."""
+        sp, lds = _mat(S, "S")
+        np_, ldn = _mat(N, "N")
+        if S.dtype != N.dtype:
+            raise ValueError("edge_score_class_pair: S and N must share a dtype")
+        n_items = item_e0.numel()
+        if n_items % items_per_block or any(t.numel() != n_items for t in (item_len, item_slot, item_row)):
+            raise ValueError("edge_score_class_pair: the item arrays must hold whole blocks of items_per_block items")
+        if fuse_softmax and (stats is None or stats.numel() < 2 * (int(slot_ptr[-1]) if n_slots is None else n_slots)):
+            raise ValueError("edge_score_class_pair: stats needs 2 elements per slot")
+        self._check(self._fn("clane_edge_score_class_pair", S.dtype)(
+            _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
+            _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
+            _vec(item_slot, torch.int32, "item_slot"), _vec(item_row, torch.int32, "item_row"),
+            n_items // items_per_block, items_per_block, _vec(class_rows, torch.int32, "class_rows"),
+            _vec(slot_ptr, torch.int64, "slot_ptr"), class_rows.numel(), row0, sp, lds, np_, ldn, d,
+            _vec(scores, S.dtype, "scores"),
+            (SCORE_FUSE_SOFTMAX | ((max(1, min(255, int(row_parts))) & 0xff) << 8)) if fuse_softmax else 0,
+            None if stats is None else _vec(stats, S.dtype, "stats"), self._stream(S)), "clane_edge_score_class_pair")
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

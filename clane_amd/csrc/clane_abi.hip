@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "projection.h"
 #include "spmm_update.h"
 
 namespace {
@@ -239,6 +240,83 @@ int edge_score_class(const int64_t *rowptr, const int32_t *colidx, const int64_t
                                                                                             stats, scores);
     }
     return check_launch("edge_score_class");
+}
+
+// ---- bilinear similarity: projection + pair K1 ----------------------------------------------------------------
+template <typename T, typename A>
+int project_rows(const T *Z, int64_t rows, int32_t d, int64_t ldz, const A *W, A *Y, int64_t ldy, void *stream) {
+    REQUIRE(rows >= 0 && d > 0 && d <= INT32_MAX / 2 && ldz >= d && ldy >= 2 * int64_t(d),
+            "project_rows: bad shape rows=%lld d=%d ldz=%lld ldy=%lld", (long long)rows, d, (long long)ldz,
+            (long long)ldy);
+    if (rows == 0) return CLANE_OK;
+    REQUIRE(Z && W && Y, "project_rows: null pointer");
+    const int n_out = 2 * d;
+    const int n_tiles = int(ceil_div(int64_t(n_out), int64_t(kProjBN)));
+    const int64_t blocks = ceil_div(rows, int64_t(kProjBM)) * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "project_rows: %lld rows is too many for one launch", (long long)rows);
+    project_rows_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(Z, rows, d, ldz, W, n_out, Y, ldy,
+                                                                                     n_tiles);
+    return check_launch("project_rows");
+}
+
+template <typename T>
+int edge_score_pair(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, int64_t row0, const T *S, int64_t lds,
+                    const T *N, int64_t ldn, int32_t d, T *scores, int32_t flags, int64_t long_threshold,
+                    const int32_t *long_rows, int64_t n_long, void *stream) {
+    REQUIRE(nrows >= 0 && row0 >= 0 && d > 0 && lds >= d && ldn >= d, "edge_score_pair: bad shape");
+    REQUIRE(long_threshold >= 0 && n_long >= 0 && n_long <= INT32_MAX, "edge_score_pair: bad long-row parameters");
+    REQUIRE(n_long == 0 || (long_rows && long_threshold > 0), "edge_score_pair: long_rows needs a list and a threshold");
+    if (nrows == 0) return CLANE_OK;
+    REQUIRE(rowptr && colidx && S && N && scores, "edge_score_pair: null pointer");
+    const Layout L = pick_layout<T>(d, {S, N}, {lds, ldn});
+    const bool fuse = (flags & CLANE_SCORE_FUSE_SOFTMAX) != 0;
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
+        constexpr int U = VEC > 1 ? 8 : 4;
+        if constexpr (LPR < kWave && VEC > 1)
+            edge_score_pair_subrow_kernel<T, VEC, LPR, U><<<row_grid(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                rowptr, colidx, nrows, row0, S, lds, N, ldn, d, scores, long_threshold, fuse, rows_per_block(nrows));
+        else
+            edge_score_pair_kernel<T, VEC, LPR, U><<<row_grid(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                rowptr, colidx, nrows, row0, S, lds, N, ldn, d, scores, long_threshold, fuse, rows_per_block(nrows));
+        if (n_long > 0)
+            edge_score_pair_long_kernel<T, VEC, LPR, U, kLongWaves>
+                <<<unsigned(n_long), kLongWaves * kWave, 0, (hipStream_t)stream>>>(rowptr, colidx, long_rows, row0, S,
+                                                                                   lds, N, ldn, d, scores, fuse);
+    });
+    return check_launch("edge_score_pair");
+}
+
+template <typename T>
+int edge_score_class_pair(const int64_t *rowptr, const int32_t *colidx, const int64_t *item_e0, const int32_t *item_len,
+                          const int32_t *item_slot, const int32_t *item_row, int64_t n_blocks, int32_t items_per_block,
+                          const int32_t *class_rows, const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const T *S,
+                          int64_t lds, const T *N, int64_t ldn, int32_t d, T *scores, int32_t flags, T *stats,
+                          void *stream) {
+    REQUIRE(n_blocks >= 0 && n_blocks <= INT32_MAX && n_rows >= 0 && n_rows <= INT32_MAX && row0 >= 0 && d > 0 &&
+                lds >= d && ldn >= d,
+            "edge_score_class_pair: bad shape");
+    REQUIRE(items_per_block >= kWavesPerBlock && items_per_block <= kMaxItemsPerBlock,
+            "edge_score_class_pair: items_per_block must be in [%d, %d]", kWavesPerBlock, kMaxItemsPerBlock);
+    if (n_rows == 0 || n_blocks == 0) return CLANE_OK;
+    const bool fuse = (flags & CLANE_SCORE_FUSE_SOFTMAX) != 0;
+    REQUIRE(colidx && item_e0 && item_len && item_slot && item_row && S && N && scores,
+            "edge_score_class_pair: null pointer");
+    REQUIRE(!fuse || (rowptr && class_rows && slot_ptr && stats),
+            "edge_score_class_pair: CLANE_SCORE_FUSE_SOFTMAX needs rowptr, class_rows, slot_ptr and stats");
+    const Layout L = pick_layout<T>(d, {S, N}, {lds, ldn});
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
+        constexpr int U = VEC > 1 ? 8 : 4;
+        edge_score_pair_class_kernel<T, VEC, LPR, U><<<unsigned(n_blocks), kBlock, 0, (hipStream_t)stream>>>(
+            colidx, item_e0, item_len, item_slot, item_row, items_per_block, row0, S, lds, N, ldn, d, scores,
+            fuse ? stats : nullptr);
+    });
+    if (fuse) {
+        int parts = (flags >> 8) & 0xff;
+        if (parts < 1) parts = 1;
+        edge_softmax_class_kernel<T><<<dim3(unsigned(n_rows), unsigned(parts)), kBlock, 0, (hipStream_t)stream>>>(
+            rowptr, class_rows, slot_ptr, stats, scores);
+    }
+    return check_launch("edge_score_class_pair");
 }
 
 template <typename A>
@@ -618,6 +696,41 @@ CLANE_EDGE_SCORE_CLASS_WRAPPER(f32, float, float, float)
 CLANE_EDGE_SCORE_CLASS_WRAPPER(f64, double, double, double)
 CLANE_EDGE_SCORE_CLASS_WRAPPER(bf16, uint16_t, bf16_t, float)
 #undef CLANE_EDGE_SCORE_CLASS_WRAPPER
+
+int clane_project_rows_f32(const float *Z, int64_t rows, int32_t d, int64_t ldz, const float *W, float *Y, int64_t ldy,
+                           void *stream) {
+    return project_rows<float, float>(Z, rows, d, ldz, W, Y, ldy, stream);
+}
+int clane_project_rows_f64(const double *Z, int64_t rows, int32_t d, int64_t ldz, const double *W, double *Y,
+                           int64_t ldy, void *stream) {
+    return project_rows<double, double>(Z, rows, d, ldz, W, Y, ldy, stream);
+}
+int clane_project_rows_bf16(const uint16_t *Z, int64_t rows, int32_t d, int64_t ldz, const float *W, float *Y,
+                            int64_t ldy, void *stream) {
+    return project_rows<bf16_t, float>(reinterpret_cast<const bf16_t *>(Z), rows, d, ldz, W, Y, ldy, stream);
+}
+
+#define CLANE_EDGE_SCORE_PAIR_WRAPPERS(SUF, T)                                                                         \
+    int clane_edge_score_pair_##SUF(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, int64_t row0,         \
+                                    const T *S, int64_t lds, const T *N, int64_t ldn, int32_t d, T *scores,            \
+                                    int32_t flags, int64_t long_threshold, const int32_t *long_rows, int64_t n_long,   \
+                                    void *stream) {                                                                    \
+        return edge_score_pair<T>(rowptr, colidx, nrows, row0, S, lds, N, ldn, d, scores, flags, long_threshold,      \
+                                  long_rows, n_long, stream);                                                          \
+    }                                                                                                                  \
+    int clane_edge_score_class_pair_##SUF(const int64_t *rowptr, const int32_t *colidx, const int64_t *item_e0,        \
+                                          const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,  \
+                                          int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,        \
+                                          const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const T *S,           \
+                                          int64_t lds, const T *N, int64_t ldn, int32_t d, T *scores, int32_t flags,   \
+                                          T *stats, void *stream) {                                                    \
+        return edge_score_class_pair<T>(rowptr, colidx, item_e0, item_len, item_slot, item_row, n_blocks,             \
+                                        items_per_block, class_rows, slot_ptr, n_rows, row0, S, lds, N, ldn, d,       \
+                                        scores, flags, stats, stream);                                                 \
+    }
+CLANE_EDGE_SCORE_PAIR_WRAPPERS(f32, float)
+CLANE_EDGE_SCORE_PAIR_WRAPPERS(f64, double)
+#undef CLANE_EDGE_SCORE_PAIR_WRAPPERS
 
 int clane_edge_score_finalize_f32(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, int64_t row0,
                                   int32_t mode, const double *sums2, const float *sq, float *scores, void *stream) {

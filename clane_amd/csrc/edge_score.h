@@ -74,19 +74,21 @@ __device__ __forceinline__ A finalize_score(A dot, int mode, A D, A nsrc, const 
 // fits one 64-edge chunk, else with a running max / sum and a second pass over the stored scores).
 // `want_stats` (a slice of a long row): leave the raw scores and hand back {max, sum of exp(score - max)} of the
 // slice, for the workgroup to combine (returned by value: a pointer that may be null kept the pair in scratch).
+// PAIR (the bilinear similarity, similarity.py:40-57): the source row is row `src_row` of S (leading dimension lds)
+// and the neighbour rows are rows of Z -- two tables instead of one; the PAIR = false instances are the cosine K1.
 // Must be called by all 64 lanes.
 template <typename A>
 struct RangeStats {
     A max, sum;
 };
 
-template <typename T, int VEC, int LPR, int U>
+template <typename T, int VEC, int LPR, int U, bool PAIR = false>
 __device__ __forceinline__ RangeStats<typename Elem<T>::acc_t> score_edge_range(const int32_t *__restrict__ colidx, int64_t ea, int64_t eb,
                                                  int64_t src_row, const T *__restrict__ Z, int64_t ldz, int d,
                                                  int mode, typename Elem<T>::acc_t D,
                                                  const typename Elem<T>::acc_t *__restrict__ sq,
                                                  typename Elem<T>::acc_t *__restrict__ scores, bool softmax,
-                                                 bool want_stats = false) {
+                                                 bool want_stats = false, const T *S = nullptr, int64_t lds = 0) {
     using A = typename Elem<T>::acc_t;
     constexpr int EPW = kWave / LPR;
     constexpr bool kTransposed = (U == 8 && LPR >= 8);
@@ -94,7 +96,11 @@ __device__ __forceinline__ RangeStats<typename Elem<T>::acc_t> score_edge_range(
     const int lane = lane_id();
     const int sub = lane / LPR, sl = lane % LPR;
     const bool single = d <= LPR * VEC;  // whole row in one pack per lane: keep the source row in registers
-    const T *zsrc = Z + src_row * ldz;
+    const T *zsrc;
+    if constexpr (PAIR)
+        zsrc = S + src_row * lds;
+    else
+        zsrc = Z + src_row * ldz;
     const A nsrc = mode == kScorePerEdge ? sqrt(sq[src_row]) : A(0);
     Pack<T, VEC> s0{};
     if (single && sl * VEC < d) s0 = k1_src_load<T, VEC>(zsrc + sl * VEC);
@@ -193,12 +199,12 @@ __device__ __forceinline__ A global_denominator(int mode, const double *__restri
 // (Round 3 tried K3's row-kernel structure here as well -- rowptr slice in LDS, rows claimed from an LDS counter, the next
 // row's first columns and source pack requested before the current row's gathers: 1.378 -> 1.401 ms at config 3, the 14
 // extra registers cost what the prefetch saved.  The static interleave stays.)
-template <typename T, int VEC, int LPR, int U>
-__global__ __launch_bounds__(kBlock) void edge_score_kernel(
+template <typename T, int VEC, int LPR, int U, bool PAIR>
+__device__ __forceinline__ void edge_score_rows(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
     const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
     const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
-    int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    int64_t long_threshold, bool fuse_softmax, int rows_per_block, const T *S, int64_t lds) {
     using A = typename Elem<T>::acc_t;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int64_t row_begin = int64_t(blockIdx.x) * rows_per_block;
@@ -208,8 +214,29 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(
         const int64_t e0 = rowptr[r];
         const int64_t e1 = rowptr[r + 1];
         if (e0 == e1 || (long_threshold > 0 && e1 - e0 > long_threshold)) continue;
-        score_edge_range<T, VEC, LPR, U>(colidx, e0, e1, row0 + r, Z, ldz, d, mode, D, sq, scores, fuse_softmax);
+        score_edge_range<T, VEC, LPR, U, PAIR>(colidx, e0, e1, row0 + r, Z, ldz, d, mode, D, sq, scores, fuse_softmax,
+                                               false, S, lds);
     }
+}
+
+template <typename T, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void edge_score_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
+    const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
+    const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
+    int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    edge_score_rows<T, VEC, LPR, U, false>(rowptr, colidx, nrows, row0, Z, ldz, d, mode, sums2, sq, scores,
+                                           long_threshold, fuse_softmax, rows_per_block, nullptr, 0);
+}
+
+// Pair scores (RAW_DOT): source rows from S, neighbour rows from N (the two halves of the projected table Y).
+template <typename T, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void edge_score_pair_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
+    const T *__restrict__ S, int64_t lds, const T *__restrict__ N, int64_t ldn, int d,
+    typename Elem<T>::acc_t *__restrict__ scores, int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    edge_score_rows<T, VEC, LPR, U, true>(rowptr, colidx, nrows, row0, N, ldn, d, kScoreRawDot, nullptr, nullptr,
+                                          scores, long_threshold, fuse_softmax, rows_per_block, S, lds);
 }
 
 // Narrow rows (LPR < 64): one SUB-WAVE per source row, 64/LPR rows per wave in flight -- the K1 counterpart
@@ -238,12 +265,12 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(
 #else
 #define CLANE_K1_BOUNDS __launch_bounds__(kBlock)
 #endif
-template <typename T, int VEC, int LPR, int U>
-__global__ CLANE_K1_BOUNDS void edge_score_subrow_kernel(
+template <typename T, int VEC, int LPR, int U, bool PAIR>
+__device__ __forceinline__ void edge_score_subrows(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
     const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
     const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
-    int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    int64_t long_threshold, bool fuse_softmax, int rows_per_block, const T *S, int64_t lds) {
     using A = typename Elem<T>::acc_t;
     static_assert(LPR < kWave && LPR >= 8 && U == 8 && LPR % U == 0, "sub-wave layout");
     constexpr int kClaim = 0, kScore = 1, kRescale = 2, kDone = 3;
@@ -330,7 +357,10 @@ __global__ CLANE_K1_BOUNDS void edge_score_subrow_kernel(
                     deg = int(dg);
                     eb = 0;
                     const int64_t gsrc = row0 + row_begin + row;
-                    s0 = k1_src_load<T, VEC>(Z + gsrc * ldz + c0s);
+                    if constexpr (PAIR)
+                        s0 = k1_src_load<T, VEC>(S + gsrc * lds + c0s);
+                    else
+                        s0 = k1_src_load<T, VEC>(Z + gsrc * ldz + c0s);
                     if (!col_ok) s0 = Pack<T, VEC>{};
                     nsrc = mode == kScorePerEdge ? sqrt(sq[gsrc]) : A(0);
                     run_m = -A(INFINITY);
@@ -380,16 +410,35 @@ __global__ CLANE_K1_BOUNDS void edge_score_subrow_kernel(
     }
 }
 
+template <typename T, int VEC, int LPR, int U>
+__global__ CLANE_K1_BOUNDS void edge_score_subrow_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
+    const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
+    const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
+    int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    edge_score_subrows<T, VEC, LPR, U, false>(rowptr, colidx, nrows, row0, Z, ldz, d, mode, sums2, sq, scores,
+                                              long_threshold, fuse_softmax, rows_per_block, nullptr, 0);
+}
+
+template <typename T, int VEC, int LPR, int U>
+__global__ CLANE_K1_BOUNDS void edge_score_pair_subrow_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t nrows, int64_t row0,
+    const T *__restrict__ S, int64_t lds, const T *__restrict__ N, int64_t ldn, int d,
+    typename Elem<T>::acc_t *__restrict__ scores, int64_t long_threshold, bool fuse_softmax, int rows_per_block) {
+    edge_score_subrows<T, VEC, LPR, U, true>(rowptr, colidx, nrows, row0, N, ldn, d, kScoreRawDot, nullptr, nullptr,
+                                             scores, long_threshold, fuse_softmax, rows_per_block, S, lds);
+}
+
 // One workgroup of WAVES waves per long row: wave w scores the 64-aligned slice w (same slicing as
 // spmm_long_kernel); a wave with an empty slice leaves at once.  Edges are independent: no fold.  With
 // `fuse_softmax` the row is soft-maxed here too: every wave keeps {max, sum exp} of its slice, the workgroup
 // combines them through LDS in wave order, and each wave rescales the scores it stored itself.
-template <typename T, int VEC, int LPR, int U, int WAVES>
-__global__ __launch_bounds__(WAVES *kWave) void edge_score_long_kernel(
+template <typename T, int VEC, int LPR, int U, int WAVES, bool PAIR>
+__device__ __forceinline__ void edge_score_long_row(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const int32_t *__restrict__ long_rows,
     int64_t row0, const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
     const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
-    bool fuse_softmax) {
+    bool fuse_softmax, const T *S, int64_t lds) {
     using A = typename Elem<T>::acc_t;
     __shared__ A s_max[WAVES], s_sum[WAVES];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -403,8 +452,9 @@ __global__ __launch_bounds__(WAVES *kWave) void edge_score_long_kernel(
     const A D = global_denominator<A>(mode, sums2);
     const bool whole_row_here = e1 - e0 <= kWave;
     const bool combine = fuse_softmax && !whole_row_here;
-    const RangeStats<A> stats = score_edge_range<T, VEC, LPR, U>(colidx, a, b, row0 + r, Z, ldz, d, mode, D, sq, scores,
-                                                                 fuse_softmax && whole_row_here, combine);
+    const RangeStats<A> stats = score_edge_range<T, VEC, LPR, U, PAIR>(colidx, a, b, row0 + r, Z, ldz, d, mode, D, sq,
+                                                                       scores, fuse_softmax && whole_row_here, combine,
+                                                                       S, lds);
     if (!combine) return;
     if (lane_id() == 0) {
         s_max[wave] = stats.max;
@@ -419,18 +469,37 @@ __global__ __launch_bounds__(WAVES *kWave) void edge_score_long_kernel(
     for (int64_t e = a + lane_id(); e < b; e += kWave) scores[e] = exp_acc<A>(scores[e] - m) / total;
 }
 
+template <typename T, int VEC, int LPR, int U, int WAVES>
+__global__ __launch_bounds__(WAVES *kWave) void edge_score_long_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const int32_t *__restrict__ long_rows,
+    int64_t row0, const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
+    const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
+    bool fuse_softmax) {
+    edge_score_long_row<T, VEC, LPR, U, WAVES, false>(rowptr, colidx, long_rows, row0, Z, ldz, d, mode, sums2, sq,
+                                                      scores, fuse_softmax, nullptr, 0);
+}
+
+template <typename T, int VEC, int LPR, int U, int WAVES>
+__global__ __launch_bounds__(WAVES *kWave) void edge_score_pair_long_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const int32_t *__restrict__ long_rows,
+    int64_t row0, const T *__restrict__ S, int64_t lds, const T *__restrict__ N, int64_t ldn, int d,
+    typename Elem<T>::acc_t *__restrict__ scores, bool fuse_softmax) {
+    edge_score_long_row<T, VEC, LPR, U, WAVES, true>(rowptr, colidx, long_rows, row0, N, ldn, d, kScoreRawDot, nullptr,
+                                                     nullptr, scores, fuse_softmax, S, lds);
+}
+
 // ---- class-affine rows (see spmm_update.h: every gathered row is read through ONE XCD's L2) ------------------
 // K1 over the same work items as K3's class pass: a wave scores the edges of one item -- a chunk of one row's edges
 // whose columns all belong to one XCD class -- with the source row in registers, exactly like a slice of
 // edge_score_long_kernel, and leaves {max, sum of exp(score - max)} of the chunk in stats[2 * slot].  Item blocks of
 // class b sit at block index 8 j + b, so XCD b only gathers rows of class b.
-template <typename T, int VEC, int LPR, int U>
-__global__ __launch_bounds__(kBlock) void edge_score_class_kernel(
+template <typename T, int VEC, int LPR, int U, bool PAIR>
+__device__ __forceinline__ void edge_score_class_items(
     const int32_t *__restrict__ colidx, const int64_t *__restrict__ item_e0, const int32_t *__restrict__ item_len,
     const int32_t *__restrict__ item_slot, const int32_t *__restrict__ item_row, int items_per_block, int64_t row0,
     const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
     const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
-    typename Elem<T>::acc_t *__restrict__ stats) {
+    typename Elem<T>::acc_t *__restrict__ stats, const T *S, int64_t lds) {
     using A = typename Elem<T>::acc_t;
     __shared__ int s_next;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -443,8 +512,9 @@ __global__ __launch_bounds__(kBlock) void edge_score_class_kernel(
         const int64_t e0 = item_e0[base + cur];
         const int len = item_len[base + cur];
         if (len > 0) {
-            const RangeStats<A> st = score_edge_range<T, VEC, LPR, U>(
-                colidx, e0, e0 + len, row0 + item_row[base + cur], Z, ldz, d, mode, D, sq, scores, false, stats != nullptr);
+            const RangeStats<A> st = score_edge_range<T, VEC, LPR, U, PAIR>(
+                colidx, e0, e0 + len, row0 + item_row[base + cur], Z, ldz, d, mode, D, sq, scores, false, stats != nullptr,
+                S, lds);
             if (stats && lane_id() == 0) {
                 const int64_t slot = item_slot[base + cur];
                 stats[2 * slot] = st.max;
@@ -455,6 +525,27 @@ __global__ __launch_bounds__(kBlock) void edge_score_class_kernel(
         if (lane_id() == 0) v = atomicAdd(&s_next, 1);
         cur = __builtin_amdgcn_readfirstlane(v);
     }
+}
+
+template <typename T, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void edge_score_class_kernel(
+    const int32_t *__restrict__ colidx, const int64_t *__restrict__ item_e0, const int32_t *__restrict__ item_len,
+    const int32_t *__restrict__ item_slot, const int32_t *__restrict__ item_row, int items_per_block, int64_t row0,
+    const T *__restrict__ Z, int64_t ldz, int d, int mode, const double *__restrict__ sums2,
+    const typename Elem<T>::acc_t *__restrict__ sq, typename Elem<T>::acc_t *__restrict__ scores,
+    typename Elem<T>::acc_t *__restrict__ stats) {
+    edge_score_class_items<T, VEC, LPR, U, false>(colidx, item_e0, item_len, item_slot, item_row, items_per_block, row0,
+                                                  Z, ldz, d, mode, sums2, sq, scores, stats, nullptr, 0);
+}
+
+template <typename T, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void edge_score_pair_class_kernel(
+    const int32_t *__restrict__ colidx, const int64_t *__restrict__ item_e0, const int32_t *__restrict__ item_len,
+    const int32_t *__restrict__ item_slot, const int32_t *__restrict__ item_row, int items_per_block, int64_t row0,
+    const T *__restrict__ S, int64_t lds, const T *__restrict__ N, int64_t ldn, int d,
+    typename Elem<T>::acc_t *__restrict__ scores, typename Elem<T>::acc_t *__restrict__ stats) {
+    edge_score_class_items<T, VEC, LPR, U, true>(colidx, item_e0, item_len, item_slot, item_row, items_per_block, row0,
+                                                 N, ldn, d, kScoreRawDot, nullptr, nullptr, scores, stats, S, lds);
 }
 
 // One workgroup per class row: the chunks' {max, sum} combined, then the row's scores become  exp(score - max) / total

@@ -20,7 +20,7 @@ from typing import Callable, Optional
 import torch
 
 from .graph import Graph
-from .similarity import CosineSimilarity, Similarity
+from .similarity import AsymmertricSimilarity, CosineSimilarity, Similarity
 
 
 class Embedder(object):
@@ -115,13 +115,15 @@ class Embedder(object):
         sim = self.similarity_measure
         if isinstance(sim, CosineSimilarity):
             return self.graph.engine(self.device, cosine_mode=sim.mode)
-        # a plug-in similarity needs whole rows: should this call be the one that creates the engine of a multi-GPU
-        # run, it divides the rows (an engine that exists already keeps its division)
+        # a plug-in similarity (and the bilinear AsymmertricSimilarity) needs whole rows: should this call be the one
+        # that creates the engine of a multi-GPU run, it divides the rows (an engine that exists already keeps its division)
         return self.graph.engine(self.device, exchange=self.graph.PLUGIN_EXCHANGE)
 
     def _build_P(self, engine) -> None:
         if isinstance(self.similarity_measure, CosineSimilarity):
             engine.build_P()                              # fused K0+K1+K2
+        elif isinstance(self.similarity_measure, AsymmertricSimilarity):
+            self.graph._build_P_bilinear(engine, self.similarity_measure)   # projection + pair K1, P stays on the card
         else:
             self.graph.build_P(self.similarity_measure)   # plugin callable + HIP softmax
 

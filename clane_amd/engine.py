@@ -102,6 +102,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self._setup_exchange(deg, fused_pack)
         self._alloc_tables(X, deg)
         self._alloc_scratch(delta_stream, overlap_chunks)
+        self._Y = None                      # projected table of build_P_bilinear, allocated by its first call
 
     # ---- constructor steps ----------------------------------------------------------------------------------
     def _choose_division(self, csr: HostCSR, X: torch.Tensor, process_group, comm, exchange: str) -> torch.Tensor:
@@ -682,6 +683,20 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 k.segment_softmax(rp, b.nrows, self.P, 0, self.score_threshold if self.long_rows[i] is not None else 0,
                                   self.long_rows[i])
         self.P_valid = True
+
+    def build_P_bilinear(self, W: torch.Tensor) -> None:
+        """P of the bilinear similarity s(u, v) = (Phi_src z_u) . (Phi_dst z_v) (AsymmertricSimilarity,
+        similarity.py:40-57) for the rows this rank owns: ``W`` = cat(Phi_src.weight, Phi_dst.weight), [2d, d].
+
+        Every row of the table (own rows and the copies of the rows they read) is projected once, Y = Z W^T on the matrix
+        cores, into a [table rows, 2d] accumulate-dtype buffer that is allocated by the first call and kept for later ones
+        -- 4 GB at 2M vertices x d = 256 in fp32 (twice the table itself), 8 GB with fp64.  Then the pair K1 scores edge
+        (r, c) as Y[r, :d] . Y[c, d:] and soft-maxes every row, over the same blocks / long rows / class rows as build_P.
+        A per-edge projection would do the d x d products E times instead of once per row (E / V = 20 at config 3).
+        Needs whole rows: a COLUMN division cannot project z_v without all of its columns.  The launches are in
+        bilinear.py (the kernel backend's optional calls)."""
+        from .bilinear import build_P_bilinear
+        build_P_bilinear(self, W)
 
     def set_cosine_mode(self, mode: str) -> None:
         """Switch between the reference's scores (global Frobenius denominators, similarity.py:35-37) and true per-edge

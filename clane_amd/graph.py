@@ -401,14 +401,19 @@ class Graph(torch.utils.data.Dataset):
         """Row-softmax of per-edge similarity as a coalesced sparse [V, V] tensor (CPU).
 
         ``CosineSimilarity`` takes the fused HIP path (K0 + K1 + K2, nothing materialised).
+        ``AsymmertricSimilarity`` takes the bilinear path (``SweepEngine.build_P_bilinear``: every row projected once
+        with the module's current weights, then the pair K1 with its fused softmax; ``forward`` is not called).
         Any other callable follows the plugin protocol literally: it is called ONCE with the
         gathered ``Z[src]``, ``Z[dst]`` batches (GPU tensors) and its scores are normalised by
         the HIP segmented softmax.
         """
-        from .similarity import CosineSimilarity
+        from .similarity import AsymmertricSimilarity, CosineSimilarity
         if isinstance(similarity, CosineSimilarity):
             eng = self.engine(cosine_mode=similarity.mode)
             eng.build_P()
+        elif isinstance(similarity, AsymmertricSimilarity):
+            eng = self.engine(exchange=self.PLUGIN_EXCHANGE) if self._engine is None else self.engine()
+            self._build_P_bilinear(eng, similarity)
         else:
             # Several GPUs: a plug-in needs WHOLE rows (all d columns of z_src and z_dst), so the rows are divided
             # (halo tables: every row a rank's edges read is in its table) and each rank scores the edges of its own
@@ -465,6 +470,14 @@ class Graph(torch.utils.data.Dataset):
             eng.P_valid = True
         values = self._gather_P(eng)
         return torch.sparse_coo_tensor(self._edge_index(), values, size=(len(self), len(self)), is_coalesced=True)
+
+    def _build_P_bilinear(self, eng, similarity) -> None:
+        """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
+        every call: a caller that changes Phi between rounds gets the new P)."""
+        n_dim = similarity.Phi_src.in_features
+        if n_dim != eng.d_full or similarity.Phi_dst.in_features != eng.d_full:
+            raise ValueError(f"AsymmertricSimilarity(n_dim={n_dim}) does not fit embeddings of dimension {eng.d_full}")
+        eng.build_P_bilinear(similarity.stacked_weight(eng.acc_dtype, eng.device))
 
     def _gather_P(self, eng) -> torch.Tensor:
         """P values of every rank, put back into the global (row, col)-sorted edge order."""

@@ -66,9 +66,10 @@ class CosineSimilarity(Similarity):
 class AsymmertricSimilarity(nn.Module, Similarity):
     """Learnable bilinear score (reference similarity.py:40-57; the class name's spelling is API).
 
-    Kept importable for configuration compatibility only: the reference can reach it solely
-    through ``IterativeEmbedder``, which fails at construction upstream, so
-    the trainable path is outside the hot path this package implements.
+    ``Graph.build_P`` / ``Embedder`` with an instance of it build P on the GPU from the CURRENT weights
+    (``SweepEngine.build_P_bilinear``: one MFMA projection of every row, then the pair K1 and its fused softmax);
+    ``forward`` is not called there.  ``__call__`` / ``forward`` stay torch, so the module can still be trained;
+    training it (``IterativeEmbedder``, which fails at construction upstream) is out of scope.
     """
 
     def __init__(self, n_dim: int, **kwargs) -> None:
@@ -80,3 +81,9 @@ class AsymmertricSimilarity(nn.Module, Similarity):
 
     def forward(self, z_src: torch.Tensor, z_dst: torch.Tensor) -> torch.Tensor:
         return (self.Phi_src(z_src) * self.Phi_dst(z_dst)).sum(-1)
+
+    def stacked_weight(self, dtype: torch.dtype, device) -> torch.Tensor:
+        """cat(Phi_src.weight, Phi_dst.weight) -- [2d, d], detached, contiguous, on ``device`` in ``dtype``: the ``W`` of
+        ``SweepEngine.build_P_bilinear`` (nn.Linear stores [out, in], so Y = Z W^T holds both projections)."""
+        W = torch.cat([self.Phi_src.weight.detach(), self.Phi_dst.weight.detach()], 0)
+        return W.to(device=device, dtype=dtype).contiguous()

@@ -38,12 +38,14 @@
 extern "C" {
 #endif
 
-#define CLANE_ABI_VERSION 4 /* 2: + clane_build_info, clane_xcc_ids, clane_check_csr, clane_spmm_update_class_*, clane_edge_score_class_*
+#define CLANE_ABI_VERSION 5 /* 2: + clane_build_info, clane_xcc_ids, clane_check_csr, clane_spmm_update_class_*, clane_edge_score_class_*
                              * 3: clane_l1_distance_* takes `sq_a` (the rows' squared norms from the outer-delta pass: free),
                              *    clane_device_alloc_contiguous; every clane_spmm_update* took `sq_out` (the same norms out of K3)
                              * 4: `sq_out` is gone again: it cost every sweep 1.1-1.4 % to save one 0.34 ms pass per build_P, and a
                              *    propagate runs >= 11 sweeps per build_P (profiles/r04_fused_norms_ab.jsonl);
-                             *    clane_spmm_update_class_* takes `flags` (CLANE_SPMM_TABLE_BEYOND_CACHE, also a flag of clane_spmm_update_*) */
+                             *    clane_spmm_update_class_* takes `flags` (CLANE_SPMM_TABLE_BEYOND_CACHE, also a flag of clane_spmm_update_*)
+                             * 5: + clane_project_rows_*, clane_edge_score_pair_*, clane_edge_score_class_pair_* (bilinear
+                             *    similarity: AsymmertricSimilarity's P without a per-edge projection) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -352,6 +354,48 @@ int clane_pair_cosine_f32(const float *A, int64_t lda, const float *B, int64_t l
                           float *out, double *ws, void *stream);
 int clane_pair_cosine_f64(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t nrows, int32_t d,
                           double *out, double *ws, void *stream);
+
+/* ---- Bilinear similarity (AsymmertricSimilarity, similarity.py:40-57): build_P (graph.py:118-128) as one row projection
+ * on the matrix cores and one pair K1 -- instead of gathering z_src / z_dst of every edge and projecting both per edge.
+ *
+ *  clane_project_rows_* : Y[r, :] = W . Z[r, :] for r < rows, i.e. Y = Z W^T.  Z: [rows, d] (leading dimension
+ *                         ldz >= d) in the table dtype; W: [2d, d] row-major in the accumulate dtype,
+ *                         W = cat(Phi_src.weight, Phi_dst.weight) (nn.Linear stores [out, in]); Y: [rows, 2d]
+ *                         (ldy >= 2d) in the accumulate dtype, columns [0, d) = Phi_src z, [d, 2d) = Phi_dst z.
+ *                         fp32 / bf16 tables: f32-input MFMA (bf16 widened on staging, W stays f32); fp64: f64 MFMA.
+ *                         Any d >= 1 and rows >= 0; no atomics, no split-K: bit-reproducible. */
+int clane_project_rows_f32(const float *Z, int64_t rows, int32_t d, int64_t ldz, const float *W, float *Y, int64_t ldy,
+                           void *stream);
+int clane_project_rows_f64(const double *Z, int64_t rows, int32_t d, int64_t ldz, const double *W, double *Y,
+                           int64_t ldy, void *stream);
+int clane_project_rows_bf16(const uint16_t *Z, int64_t rows, int32_t d, int64_t ldz, const float *W, float *Y,
+                            int64_t ldy, void *stream);
+
+/*  clane_edge_score_pair_* : K1 of clane_edge_score_* with two tables -- the score of edge (r, c) is the raw dot of
+ *                            S[row0 + r, 0:d) and N[c, 0:d) (the bilinear score (Phi_src z_r) . (Phi_dst z_c) when
+ *                            S = Y, N = Y + d, lds = ldn = ldy), no denominators.  rowptr / colidx / long rows /
+ *                            flags (CLANE_SCORE_FUSE_SOFTMAX) exactly as clane_edge_score_*.  No bf16 instance: Y is
+ *                            always in the accumulate dtype.
+ *  clane_edge_score_class_pair_* : the same over the class rows' work items, as clane_edge_score_class_*. */
+int clane_edge_score_pair_f32(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, int64_t row0, const float *S,
+                              int64_t lds, const float *N, int64_t ldn, int32_t d, float *scores, int32_t flags,
+                              int64_t long_threshold, const int32_t *long_rows, int64_t n_long, void *stream);
+int clane_edge_score_pair_f64(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, int64_t row0,
+                              const double *S, int64_t lds, const double *N, int64_t ldn, int32_t d, double *scores,
+                              int32_t flags, int64_t long_threshold, const int32_t *long_rows, int64_t n_long,
+                              void *stream);
+int clane_edge_score_class_pair_f32(const int64_t *rowptr, const int32_t *colidx, const int64_t *item_e0,
+                                    const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                    int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                    const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const float *S, int64_t lds,
+                                    const float *N, int64_t ldn, int32_t d, float *scores, int32_t flags, float *stats,
+                                    void *stream);
+int clane_edge_score_class_pair_f64(const int64_t *rowptr, const int32_t *colidx, const int64_t *item_e0,
+                                    const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                    int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                    const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const double *S,
+                                    int64_t lds, const double *N, int64_t ldn, int32_t d, double *scores,
+                                    int32_t flags, double *stats, void *stream);
 
 #ifdef __cplusplus
 }
