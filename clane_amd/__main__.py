@@ -18,7 +18,7 @@ import torch
 import yaml
 
 from . import similarity
-from .embedder import Embedder, IterativeEmbedder
+from .embedder import AlternatingEmbedder, Embedder, IterativeEmbedder
 from .graph import Graph
 
 
@@ -78,7 +78,11 @@ def embedding(args):
     similarity_measure = similarity_measure(**hparams['similarity']['kwargs'])
 
     embedder_cls = IterativeEmbedder if hasattr(similarity_measure, 'parameters') else Embedder
-    extra = {"num_workers": args.num_workers} if embedder_cls is IterativeEmbedder else {}
+    if embedder_cls is IterativeEmbedder and getattr(args, "train_similarity", False):
+        if world > 1:
+            raise NotImplementedError("--train_similarity runs on one GPU only; several GPUs are out of scope")
+        embedder_cls = AlternatingEmbedder          # trains on the GPU, alternating with propagation
+    extra = {"num_workers": args.num_workers} if embedder_cls is not Embedder else {}
     if world > 1 and getattr(args, "exchange", "auto") != "auto":
         g.engine(device if device.type == "cuda" else None, exchange=args.exchange)     # first use fixes the division
     if args.init_Z is not None:                     # resume: start from saved embeddings instead of Z = X
@@ -144,6 +148,11 @@ def get_parser():
                              "Z (no exchange per sweep; what auto picks for wide rows), rows with one all-gather of the "
                              "updated rows per sweep (allgather_all) or the leaner row splits; "
                              "see DESIGN.md section 6.  A plug-in similarity needs a row division (default then: halo).")
+    parser.add_argument("--train_similarity", action='store_true',
+                        help="(extension) with a similarity that has parameters (AsymmertricSimilarity): train it on the "
+                             "GPU, alternating with propagation (AlternatingEmbedder; the config's embedder keys are the "
+                             "reference's: tolerence, tolerence_Z, tolerence_P, epoch, batch_size, lr).  One GPU only.  "
+                             "Without the flag such a config ends as before: IterativeEmbedder is not implemented.")
     parser.add_argument("--gpu", action='store_true')
     return parser
 

@@ -80,6 +80,14 @@ for _s in ("f32", "f64"):
         C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _i32, _p, _p])
 for _s in ("f32", "f64", "bf16"):
     SIGNATURES[f"clane_project_rows_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p])
+    # training the bilinear similarity (csrc/pair_train.h)
+    SIGNATURES[f"clane_pair_project_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _p, _p, _p])
+    SIGNATURES[f"clane_pair_grad_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p])
+for _s in ("f32", "f64"):
+    SIGNATURES[f"clane_pair_loss_{_s}"] = (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p])
+    SIGNATURES[f"clane_adam_step_{_s}"] = (C.c_int, [_p, _p, _p, _p, _i64, C.c_double, _p, _p, _p])
+SIGNATURES["clane_pair_grad_ws_len"] = (_i64, [_i64, _i32])
+SIGNATURES["clane_pair_labels"] = (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p])
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
 _ACC = {torch.float32: torch.float32, torch.float64: torch.float64, torch.bfloat16: torch.float32}
@@ -338,6 +346,33 @@ class KernelBackend(abc.ABC):
                               n_slots=None, row_parts=1):
         """edge_score_class with two tables, as edge_score_pair."""
         raise NotImplementedError(f"{type(self).__name__} has no edge_score_class_pair")
+
+    # training the bilinear similarity (train.py): optional in the same way -- SimilarityTrainer / PairSampler are the
+    # only callers.  Pairs are TABLE ROWS (int32), linked / mask uint8, u / A / Bm / g / W / dW in the accumulate dtype.
+    def pair_project(self, Z, d: int, src, dst, W, A, Bm):
+        """A[k] = W[:d] . Z[src[k], :d], Bm[k] = W[d:] . Z[dst[k], :d] for the src.numel() pairs (A, Bm: [B, d])."""
+        raise NotImplementedError(f"{type(self).__name__} has no pair_project")
+
+    def pair_loss(self, A, Bm, d: int, linked, u, g, mask, ws, stats):
+        """Per pair s = A[k] . Bm[k], the masked log loss of embedder.py:276-282 and g = d loss / d s; stats = {sum of
+        the masked losses, M} (float64 [2]); ws: reduce_ws_len() float64."""
+        raise NotImplementedError(f"{type(self).__name__} has no pair_loss")
+
+    def pair_grad_ws_len(self, B: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no pair_grad_ws_len")
+
+    def pair_grad(self, Z, d: int, src, dst, A, Bm, g, stats, ws, dW):
+        """dW [2d, d] = the gradient of the mean masked loss; M = stats[1] is read on the device, M = 0 gives zeros."""
+        raise NotImplementedError(f"{type(self).__name__} has no pair_grad")
+
+    def adam_step(self, W, m, v, dW, lr: float, stats, state):
+        """One torch.optim.Adam (defaults) step; state = {steps taken, sum of step losses} (float64 [2]); stats[1] == 0:
+        nothing changes."""
+        raise NotImplementedError(f"{type(self).__name__} has no adam_step")
+
+    def pair_labels(self, rowptr, colidx, nrows: int, src, dst, linked):
+        """linked[k] = dst[k] is a column of row src[k] of a CSR with sorted, unique rows."""
+        raise NotImplementedError(f"{type(self).__name__} has no pair_labels")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -646,6 +681,73 @@ class HipKernels(KernelBackend):
             _vec(scores, S.dtype, "scores"),
             (SCORE_FUSE_SOFTMAX | ((max(1, min(255, int(row_parts))) & 0xff) << 8)) if fuse_softmax else 0,
             None if stats is None else _vec(stats, S.dtype, "stats"), self._stream(S)), "clane_edge_score_class_pair")
+
+    # -- training the bilinear similarity ------------------------------------------------
+    @staticmethod
+    def _pairs(src, dst, what: str) -> int:
+        if src.numel() != dst.numel():
+            raise ValueError(f"{what}: src and dst must have one entry per pair")
+        return src.numel()
+
+    def _pair_mats(self, A, Bm, B: int, d: int, acc, what: str):
+        for t, name in ((A, "A"), (Bm, "Bm")):
+            if t.dtype != acc or not t.is_contiguous() or t.numel() < B * d:
+                raise ValueError(f"{what}: {name} must be a contiguous {acc} tensor of at least B * d elements")
+        return A.data_ptr(), Bm.data_ptr()
+
+    def pair_project(self, Z, d: int, src, dst, W, A, Bm):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        B = self._pairs(src, dst, "pair_project")
+        if tuple(W.shape) != (2 * d, d):
+            raise ValueError(f"pair_project: W must be [2d, d] = [{2 * d}, {d}], got {tuple(W.shape)}")
+        ap, bp = self._pair_mats(A, Bm, B, d, acc, "pair_project")
+        self._invoke(self._fn("clane_pair_project", Z.dtype), "clane_pair_project",
+                     zp, Z.shape[0], d, ldz, _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B,
+                     _vec(W, acc, "W"), ap, bp, self._stream(Z))
+
+    def pair_loss(self, A, Bm, d: int, linked, u, g, mask, ws, stats):
+        B = linked.numel()
+        acc = A.dtype
+        ap, bp = self._pair_mats(A, Bm, B, d, acc, "pair_loss")
+        if u.numel() != B or g.numel() < B or mask.numel() < B or stats.numel() < 2 or ws.numel() < self.reduce_ws_len():
+            raise ValueError("pair_loss: u, g, mask need one entry per pair, stats 2 and ws reduce_ws_len() doubles")
+        self._invoke(self._fn("clane_pair_loss", acc), "clane_pair_loss",
+                     ap, bp, B, d, _vec(linked, torch.uint8, "linked"), _vec(u, acc, "u"), _vec(g, acc, "g"),
+                     _vec(mask, torch.uint8, "mask"), _vec(ws, torch.float64, "ws"), _vec(stats, torch.float64, "stats"),
+                     self._stream(A))
+
+    def pair_grad_ws_len(self, B: int, d: int) -> int:
+        return int(self.lib.clane_pair_grad_ws_len(B, d))
+
+    def pair_grad(self, Z, d: int, src, dst, A, Bm, g, stats, ws, dW):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        B = self._pairs(src, dst, "pair_grad")
+        ap, bp = self._pair_mats(A, Bm, B, d, acc, "pair_grad")
+        if g.numel() < B or ws.numel() < self.pair_grad_ws_len(B, d) or dW.numel() != 2 * d * d:
+            raise ValueError("pair_grad: g needs one entry per pair, ws pair_grad_ws_len(B, d) elements, dW 2 d^2")
+        self._invoke(self._fn("clane_pair_grad", Z.dtype), "clane_pair_grad",
+                     zp, Z.shape[0], d, ldz, _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B, ap, bp,
+                     _vec(g, acc, "g"), _vec(stats, torch.float64, "stats"), _vec(ws, acc, "ws"), _vec(dW, acc, "dW"),
+                     self._stream(Z))
+
+    def adam_step(self, W, m, v, dW, lr: float, stats, state):
+        if not (W.numel() == m.numel() == v.numel() == dW.numel()) or state.numel() < 2:
+            raise ValueError("adam_step: W, m, v, dW must have one length, state 2 doubles")
+        self._invoke(self._fn("clane_adam_step", W.dtype), "clane_adam_step",
+                     _vec(W, W.dtype, "W"), _vec(m, W.dtype, "m"), _vec(v, W.dtype, "v"), _vec(dW, W.dtype, "dW"),
+                     W.numel(), float(lr), _vec(stats, torch.float64, "stats"), _vec(state, torch.float64, "state"),
+                     self._stream(W))
+
+    def pair_labels(self, rowptr, colidx, nrows: int, src, dst, linked):
+        B = self._pairs(src, dst, "pair_labels")
+        if rowptr.numel() < nrows + 1 or linked.numel() < B:
+            raise ValueError("pair_labels: rowptr needs nrows + 1 entries, linked one per pair")
+        self._invoke(self.lib.clane_pair_labels, "clane_pair_labels",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), nrows,
+                     _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B,
+                     _vec(linked, torch.uint8, "linked"), self._stream(linked))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

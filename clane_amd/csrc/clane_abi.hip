@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "pair_train.h"
 #include "projection.h"
 #include "spmm_update.h"
 
@@ -568,6 +569,68 @@ int pair_cosine(const T *A, int64_t lda, const T *B, int64_t ldb, int64_t nrows,
     return check_launch("pair_cosine");
 }
 
+// ---- training step of the bilinear similarity (pair_train.h) -----------------------------------------------------
+template <typename T, typename A>
+int pair_project(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src, const int32_t *dst,
+                 int64_t B, const A *W, A *PA, A *PB, void *stream) {
+    REQUIRE(table_rows >= 0 && B >= 0 && d > 0 && d <= 32768 && ldz >= d, "pair_project: bad shape rows=%lld B=%lld d=%d ldz=%lld",
+            (long long)table_rows, (long long)B, d, (long long)ldz);
+    if (B == 0) return CLANE_OK;
+    REQUIRE(Z && src && dst && W && PA && PB, "pair_project: null pointer");
+    const int n_tiles = int(ceil_div(int64_t(d), int64_t(kProjBN)));
+    const int64_t blocks = ceil_div(B, int64_t(kProjBM)) * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "pair_project: %lld pairs is too many for one launch", (long long)B);
+    pair_project_kernel<T, A><<<dim3(unsigned(blocks), 2), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, src, dst, B, W, PA, PB, n_tiles);
+    return check_launch("pair_project");
+}
+
+template <typename A>
+int pair_loss(const A *PA, const A *PB, int64_t B, int32_t d, const uint8_t *linked, const A *u, A *g, uint8_t *mask,
+              double *ws, double *stats, void *stream) {
+    REQUIRE(B >= 0 && d > 0, "pair_loss: bad shape B=%lld d=%d", (long long)B, d);
+    REQUIRE(ws && stats, "pair_loss: null workspace/output");
+    REQUIRE(B == 0 || (PA && PB && linked && u && g && mask), "pair_loss: null pointer");
+    int grid = int(ceil_div(B > 0 ? B : 1, kBlock / kPairLanes));
+    if (grid > kReduceGrid) grid = kReduceGrid;
+    pair_loss_kernel<A><<<grid, kBlock, 0, (hipStream_t)stream>>>(PA, PB, B, d, linked, u, g, mask, ws);
+    reduce_fixed_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(ws, grid, grid, 2, stats);
+    return check_launch("pair_loss");
+}
+
+inline int64_t pair_grad_chunks(int64_t B) { return ceil_div(B > 0 ? B : 1, int64_t(kGradChunk)); }
+
+template <typename T, typename A>
+int pair_grad(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src, const int32_t *dst, int64_t B,
+              const A *PA, const A *PB, const A *g, const double *stats, A *ws, A *dW, void *stream) {
+    REQUIRE(table_rows >= 0 && B >= 0 && d > 0 && d <= 32768 && ldz >= d, "pair_grad: bad shape rows=%lld B=%lld d=%d ldz=%lld",
+            (long long)table_rows, (long long)B, d, (long long)ldz);
+    REQUIRE(stats && ws && dW, "pair_grad: null stats/workspace/output");
+    REQUIRE(B == 0 || (Z && src && dst && PA && PB && g), "pair_grad: null pointer");
+    const int64_t n_chunks = B > 0 ? pair_grad_chunks(B) : 0;
+    REQUIRE(n_chunks <= 65535, "pair_grad: %lld pairs is too many for one launch", (long long)B);
+    const int n_tiles = int(ceil_div(int64_t(d), int64_t(kProjBN)));
+    const int64_t n = 2 * int64_t(d) * d;
+    if (n_chunks > 0)
+        pair_grad_kernel<T, A><<<dim3(unsigned(n_tiles * n_tiles), 2, unsigned(n_chunks)), kBlock, 0,
+                                 (hipStream_t)stream>>>(Z, table_rows, d, ldz, src, dst, B, PA, PB, g, ws, n_tiles);
+    pair_grad_reduce_kernel<A><<<unsigned(ceil_div(n, kBlock)), kBlock, 0, (hipStream_t)stream>>>(ws, n_chunks, n, stats,
+                                                                                               dW);
+    return check_launch("pair_grad");
+}
+
+template <typename A>
+int adam_step(A *W, A *m, A *v, const A *dW, int64_t n, double lr, const double *stats, double *state, void *stream) {
+    REQUIRE(n >= 0 && n <= int64_t(INT32_MAX) * kBlock, "adam_step: bad length %lld", (long long)n);
+    REQUIRE(stats && state, "adam_step: null stats/state");
+    REQUIRE(n == 0 || (W && m && v && dW), "adam_step: null pointer");
+    if (n > 0)
+        adam_step_kernel<A><<<unsigned(ceil_div(n, kBlock)), kBlock, 0, (hipStream_t)stream>>>(W, m, v, dW, n, lr, stats,
+                                                                                            state);
+    adam_finish_kernel<<<1, kWave, 0, (hipStream_t)stream>>>(stats, state);
+    return check_launch("adam_step");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -855,6 +918,45 @@ int clane_pair_cosine_f32(const float *A, int64_t lda, const float *B, int64_t l
 int clane_pair_cosine_f64(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t nrows, int32_t d,
                           double *out, double *ws, void *stream) {
     return pair_cosine<double>(A, lda, B, ldb, nrows, d, out, ws, stream);
+}
+
+#define CLANE_PAIR_TRAIN_WRAPPERS(SUF, CT, T, AT)                                                                      \
+    int clane_pair_project_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,         \
+                                 const int32_t *dst, int64_t B, const AT *W, AT *A, AT *Bm, void *stream) {           \
+        return pair_project<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, src, dst, B, W, A, Bm,         \
+                                   stream);                                                                           \
+    }                                                                                                                 \
+    int clane_pair_grad_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,            \
+                              const int32_t *dst, int64_t B, const AT *A, const AT *Bm, const AT *g,                  \
+                              const double *stats, AT *ws, AT *dW, void *stream) {                                    \
+        return pair_grad<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, src, dst, B, A, Bm, g, stats, ws, \
+                                dW, stream);                                                                          \
+    }
+CLANE_PAIR_TRAIN_WRAPPERS(f32, float, float, float)
+CLANE_PAIR_TRAIN_WRAPPERS(f64, double, double, double)
+CLANE_PAIR_TRAIN_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_PAIR_TRAIN_WRAPPERS
+#define CLANE_PAIR_LOSS_WRAPPERS(SUF, AT)                                                                              \
+    int clane_pair_loss_##SUF(const AT *A, const AT *Bm, int64_t B, int32_t d, const uint8_t *linked, const AT *u,    \
+                              AT *g, uint8_t *mask, double *ws, double *stats, void *stream) {                        \
+        return pair_loss<AT>(A, Bm, B, d, linked, u, g, mask, ws, stats, stream);                                     \
+    }                                                                                                                 \
+    int clane_adam_step_##SUF(AT *W, AT *m, AT *v, const AT *dW, int64_t n, double lr, const double *stats,           \
+                              double *state, void *stream) {                                                          \
+        return adam_step<AT>(W, m, v, dW, n, lr, stats, state, stream);                                               \
+    }
+CLANE_PAIR_LOSS_WRAPPERS(f32, float)
+CLANE_PAIR_LOSS_WRAPPERS(f64, double)
+#undef CLANE_PAIR_LOSS_WRAPPERS
+int64_t clane_pair_grad_ws_len(int64_t B, int32_t d) { return pair_grad_chunks(B) * 2 * int64_t(d) * d; }
+int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, const int32_t *src,
+                      const int32_t *dst, int64_t B, uint8_t *linked, void *stream) {
+    REQUIRE(nrows >= 0 && B >= 0, "pair_labels: bad shape nrows=%lld B=%lld", (long long)nrows, (long long)B);
+    if (B == 0) return CLANE_OK;
+    REQUIRE(rowptr && colidx && src && dst && linked, "pair_labels: null pointer");
+    pair_labels_kernel<<<grid_for_waves(ceil_div(B, kWave)), kBlock, 0, (hipStream_t)stream>>>(rowptr, colidx, nrows,
+                                                                                              src, dst, B, linked);
+    return check_launch("pair_labels");
 }
 
 }  // extern "C"

@@ -127,6 +127,69 @@ class Embedder(object):
         else:
             self.graph.build_P(self.similarity_measure)   # plugin callable + HIP softmax
 
+    # ---- training the similarity (reference embedder.py:249-289) --------------------------------------------------
+    def _pair_sampler(self, engine):
+        """The sampler of this embedder's own training calls: made once, so that successive calls draw new epochs."""
+        if getattr(self, "_sampler", None) is None or self._sampler.eng is not engine:
+            from .train import PairSampler
+            gen = torch.Generator(device=engine.device)
+            gen.manual_seed(int(getattr(self, "seed", 0)))
+            self._sampler = PairSampler(engine, self.batch_size, gen, float(getattr(self, "positive_fraction", 0.0)))
+        return self._sampler
+
+    def update_similarity_measure(self, epochs: Optional[int] = None, sampler=None, replay=None):
+        """Train the AsymmertricSimilarity on the current embeddings for ``epochs`` epochs (default: ``self.epoch``, else 1)
+        with a fresh Adam (the reference builds a new optimizer per call, embedder.py:259) and return the per-epoch
+        losses as the reference reports them: the sum of the step losses over the index of the epoch's last step
+        (embedder.py:287; a one-step epoch divides by 1).  The steps run in HIP kernels on the engine; the host reads one
+        scalar per epoch.  Afterwards the weights are copied back into ``Phi_src.weight`` / ``Phi_dst.weight``.
+
+        ``sampler``: a ``train.PairSampler`` (default: one seeded with ``self.seed``, kept between calls).
+        ``replay``: [(src, dst, linked, trial), ...] in VERTEX ids -- exactly these steps are run instead,
+        ``len(replay) / epochs`` per epoch; ``trial`` holds the recorded Bernoulli outcomes (embedder.py:278)."""
+        from .train import require_one_gpu, rows_of_vertices
+        sim = self.similarity_measure
+        if not isinstance(sim, AsymmertricSimilarity):
+            raise TypeError(f"update_similarity_measure trains an AsymmertricSimilarity, not a {type(sim).__name__}")
+        engine = self._engine()
+        require_one_gpu(engine)
+        if sim.Phi_src.in_features != engine.d_full:
+            raise ValueError(f"AsymmertricSimilarity(n_dim={sim.Phi_src.in_features}) does not fit embeddings of "
+                             f"dimension {engine.d_full}")
+        epochs = int(getattr(self, "epoch", 1) if epochs is None else epochs)
+        if epochs < 1:
+            raise ValueError("update_similarity_measure: at least one epoch")
+        W0 = sim.stacked_weight(engine.acc_dtype, engine.device)
+        if replay is not None:
+            if len(replay) == 0 or len(replay) % epochs:
+                raise ValueError(f"replay: {len(replay)} steps do not divide into {epochs} epochs")
+            dev, acc = engine.device, engine.acc_dtype
+            steps = [(rows_of_vertices(engine, s), rows_of_vertices(engine, t),
+                      torch.as_tensor(l).to(dev, torch.uint8).contiguous(),
+                      # a recorded success is replayed with u = 0 (0 < p), a failure with u = 1 (1 < p never holds)
+                      1.0 - torch.as_tensor(b).to(dev, acc).contiguous()) for s, t, l, b in replay]
+            per_epoch = len(steps) // epochs
+            trainer = engine.similarity_trainer(W0, self.lr, max(s[0].numel() for s in steps))
+            batches = lambda e: steps[e * per_epoch:(e + 1) * per_epoch]     # noqa: E731
+        else:
+            sampler = sampler if sampler is not None else self._pair_sampler(engine)
+            trainer = engine.similarity_trainer(W0, self.lr, sampler.batch_size)
+            batches = lambda e: sampler.epoch()                              # noqa: E731
+        losses = []
+        for e in range(epochs):
+            n_steps = 0
+            for src, dst, linked, u in batches(e):
+                trainer.step(src, dst, linked, u)
+                n_steps += 1
+            losses.append(trainer.epoch_loss() / max(n_steps - 1, 1))
+        W = trainer.weights()
+        d = engine.d_full
+        with torch.no_grad():
+            sim.Phi_src.weight.copy_(W[:d].to(sim.Phi_src.weight.device, sim.Phi_src.weight.dtype))
+            sim.Phi_dst.weight.copy_(W[d:].to(sim.Phi_dst.weight.device, sim.Phi_dst.weight.dtype))
+        self.last_trainer = trainer
+        return losses
+
     def iterate(self):
         """Outer fixed point (reference embedder.py:56-69)."""
         engine = self._engine()
@@ -367,3 +430,80 @@ class IterativeEmbedder(Embedder):
         raise NotImplementedError(
             "IterativeEmbedder (trainable AsymmertricSimilarity) is not part of the MI355X hot path; the "
             "reference's own implementation fails at construction. Use CosineSimilarity with Embedder.")
+
+
+class AlternatingEmbedder(Embedder):
+    """Alternate "train the similarity" and "propagate with it" -- what the reference's ``IterativeEmbedder``
+    (embedder.py:158-247) sets out to do, as a class of its own: upstream's fails in ``__init__`` and calls a method
+    that does not exist, and ``IterativeEmbedder`` above stays the stub it was.  Hyper-parameter names are the
+    reference's.  One round:
+
+    1. ``update_similarity_measure(epoch)`` until ``tolerence_P`` consecutive calls bring no new minimum of the last
+       epoch's loss (embedder.py:206-218);
+    2. ``propagate()``: P from the new weights (``build_P_bilinear``) and sweeps until ``tolerence_Z`` consecutive
+       sweeps bring no new minimum of the L1 delta (what ``update_embeddings`` evidently meant);
+    3. the global rule of ``Embedder.iterate``: the distance of the embeddings from the round's start, ``tolerence``
+       rounds without a new minimum end the run (``max_rounds`` caps it).
+
+    Records ``train_losses`` (per round: the per-epoch losses of every training call), ``sweep_counts`` and
+    ``outer_deltas``.  One GPU only."""
+
+    def __init__(self, graph, similarity_measure, device, gamma: float = 0.76, tolerence: int = 10,
+                 tolerence_Z: Optional[int] = None, tolerence_P: int = 1, epoch: int = 1, batch_size: int = 4,
+                 lr: float = 1e-4, seed: int = 0, positive_fraction: float = 0.0, max_rounds: Optional[int] = None,
+                 num_workers: int = 0, save_history: bool = False, verbose: bool = True,
+                 max_sweeps: Optional[int] = None, **embedder_kwargs) -> None:
+        if not isinstance(similarity_measure, AsymmertricSimilarity):
+            raise TypeError(f"AlternatingEmbedder trains an AsymmertricSimilarity, not a "
+                            f"{type(similarity_measure).__name__}")
+        super().__init__(graph, similarity_measure, device, gamma=gamma, tolerence=tolerence, batch_size=batch_size,
+                         lr=lr, num_workers=num_workers, save_history=save_history, verbose=verbose,
+                         max_sweeps=max_sweeps, **embedder_kwargs)
+        self.tolerence = tolerence
+        self.tolerence_Z = tolerence if tolerence_Z is None else tolerence_Z
+        self.tolerence_P = tolerence_P
+        if min(self.tolerence, self.tolerence_Z, self.tolerence_P, epoch) < 1:
+            raise ValueError("AlternatingEmbedder: tolerence, tolerence_Z, tolerence_P and epoch must be at least 1")
+        self.tolerences["propagation"] = self.Tolerence(self.tolerence_Z)
+        self.tolerences["similarity_model"] = self.Tolerence(self.tolerence_P)
+        self.epoch, self.seed, self.positive_fraction, self.max_rounds = epoch, seed, positive_fraction, max_rounds
+        self.train_losses = []
+
+    def train_similarity(self):
+        """Step 1 of a round; returns the per-epoch losses of every call it made."""
+        tol = self.tolerences["similarity_model"]
+        tol.reset()
+        best, calls = math.inf, []
+        while True:
+            losses = self.update_similarity_measure(self.epoch)
+            calls.append(losses)
+            if losses[-1] >= best or math.isnan(losses[-1]):
+                tol.endure()
+            else:
+                best = losses[-1]
+                tol.reset()
+            if self.verbose:
+                print(f"similarity loss {losses[-1]:.6f}", tol.value)
+            if tol.value == 0:
+                return calls
+
+    def iterate(self):
+        engine = self._engine()
+        from .train import require_one_gpu
+        require_one_gpu(engine)
+        rounds = 0
+        while True:
+            engine.snapshot()
+            self.train_losses.append(self.train_similarity())
+            self.propagate()
+            amount = engine.distance_from_snapshot()
+            self.outer_deltas.append(amount)
+            if self.minimum_amount_updated_Z > amount:
+                self.tolerences["global"].reset()
+                self.minimum_amount_updated_Z = amount
+            else:
+                self.tolerences["global"].endure()
+            rounds += 1
+            if self.tolerences["global"].value == 0 or (self.max_rounds and rounds >= self.max_rounds):
+                break
+        self.flush_history()

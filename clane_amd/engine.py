@@ -698,6 +698,13 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         from .bilinear import build_P_bilinear
         build_P_bilinear(self, W)
 
+    def similarity_trainer(self, W0: torch.Tensor, lr: float, batch_size: int = 4):
+        """Optimizer state for training the bilinear similarity on this engine's current embeddings (train.py):
+        ``step(src_rows, dst_rows, linked, u)``, ``epoch_loss()``, ``weights()``.  ``W0`` = cat(Phi_src.weight,
+        Phi_dst.weight), [2d, d]; Adam starts fresh.  One GPU only."""
+        from .train import SimilarityTrainer
+        return SimilarityTrainer(self, W0, lr, batch_size)
+
     def set_cosine_mode(self, mode: str) -> None:
         """Switch between the reference's scores (global Frobenius denominators, similarity.py:35-37) and true per-edge
         cosine for the NEXT build_P; the row layout does not depend on it."""

@@ -68,8 +68,10 @@ class AsymmertricSimilarity(nn.Module, Similarity):
 
     ``Graph.build_P`` / ``Embedder`` with an instance of it build P on the GPU from the CURRENT weights
     (``SweepEngine.build_P_bilinear``: one MFMA projection of every row, then the pair K1 and its fused softmax);
-    ``forward`` is not called there.  ``__call__`` / ``forward`` stay torch, so the module can still be trained;
-    training it (``IterativeEmbedder``, which fails at construction upstream) is out of scope.
+    ``forward`` is not called there.  ``__call__`` / ``forward`` stay torch.  Training runs on the GPU as well:
+    ``Embedder.update_similarity_measure`` / ``AlternatingEmbedder`` (train.py, csrc/pair_train.h) take the weights from
+    this module and copy the trained ones back; ``IterativeEmbedder`` itself stays a stub (it fails at construction
+    upstream).
     """
 
     def __init__(self, n_dim: int, **kwargs) -> None:

@@ -45,7 +45,10 @@ extern "C" {
                              *    propagate runs >= 11 sweeps per build_P (profiles/r04_fused_norms_ab.jsonl);
                              *    clane_spmm_update_class_* takes `flags` (CLANE_SPMM_TABLE_BEYOND_CACHE, also a flag of clane_spmm_update_*)
                              * 5: + clane_project_rows_*, clane_edge_score_pair_*, clane_edge_score_class_pair_* (bilinear
-                             *    similarity: AsymmertricSimilarity's P without a per-edge projection) */
+                             *    similarity: AsymmertricSimilarity's P without a per-edge projection)
+                             * 5, additions that change no existing call (the number stays: every v5 caller keeps working):
+                             *    + clane_pair_project_*, clane_pair_loss_*, clane_pair_grad_*, clane_pair_grad_ws_len,
+                             *    clane_adam_step_*, clane_pair_labels (training the bilinear similarity on the device) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -396,6 +399,60 @@ int clane_edge_score_class_pair_f64(const int64_t *rowptr, const int32_t *colidx
                                     const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const double *S,
                                     int64_t lds, const double *N, int64_t ldn, int32_t d, double *scores,
                                     int32_t flags, double *stats, void *stream);
+
+/* ---- Training the bilinear similarity (IterativeEmbedder.update_similarity_measure, embedder.py:249-289) on explicit
+ * pairs, without a host decision per step.  A batch is B pairs (src[k], dst[k]) of TABLE ROWS (int32; a row outside
+ * [0, table_rows) is read as a zero row), linked[k] (uint8: the pair is an edge), u[k] (accumulate dtype, uniform in
+ * [0, 1): the Bernoulli trial of embedder.py:278 succeeds where u < p; a recorded trial is replayed with u = 0 for a
+ * success and u = 1 for a failure).  W = cat(Phi_src.weight, Phi_dst.weight), [2d, d] row-major, accumulate dtype.
+ * No allocation, no atomics, every sum in a fixed order: two calls give the same bits.
+ *
+ *  clane_pair_project_* : A[k, :] = Phi_src . Z[src[k], 0:d), Bm[k, :] = Phi_dst . Z[dst[k], 0:d), both [B, d]
+ *                         contiguous in the accumulate dtype.  The MFMA tiling of clane_project_rows_* with the rows
+ *                         taken through the index lists: nothing of the size of the table is touched.
+ *  clane_pair_loss_*    : s = A[k] . Bm[k], p = sigmoid(s), q = sigmoid(-s) (never 1 - p), mask = linked XOR (u < p),
+ *                         loss_k = -log((linked ? p : q) + 1e-10) (embedder.py:276-279);
+ *                         g[k] = d loss_k / d s = linked ? -p q / (p + 1e-10) : p q / (q + 1e-10), 0 where mask is 0;
+ *                         stats[0] = sum of mask * loss_k, stats[1] = M = sum of mask, in double.
+ *                         ws: clane_reduce_ws_len() doubles.
+ *  clane_pair_grad_*    : the gradient of mean over the masked pairs of loss_k (embedder.py:282-283):
+ *                         dW[0:d, :] = (1/M) sum_k g_k Bm[k, :]^T Z[src[k], :], dW[d:2d, :] = (1/M) sum_k g_k A[k, :]^T
+ *                         Z[dst[k], :], M read from stats[1] on the device; M = 0 gives dW = 0.  Chunks of 2048 pairs are
+ *                         contracted by separate workgroups (MFMA) into ws (clane_pair_grad_ws_len(B, d) accumulate-
+ *                         dtype elements) and added in chunk order.
+ *  clane_adam_step_*    : one step of torch.optim.Adam with its defaults (betas 0.9 / 0.999, eps 1e-8, no weight decay,
+ *                         no amsgrad) on W, m, v of n elements (embedder.py:259, :285).  state[0] = steps taken so far,
+ *                         state[1] = sum of the step losses since the caller zeroed it (embedder.py:286): the step adds
+ *                         1 and stats[0] / M.  stats[1] == 0: nothing changes at all -- the `continue` of
+ *                         embedder.py:280-281 without the host looking.
+ *  clane_pair_labels    : linked[k] = dst[k] in colidx[rowptr[src[k]] .. rowptr[src[k] + 1]) by binary search -- what
+ *                         graph.py:99 means; the rows of this CSR must be sorted and unique (src outside [0, nrows): 0). */
+int clane_pair_project_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                           const int32_t *dst, int64_t B, const float *W, float *A, float *Bm, void *stream);
+int clane_pair_project_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                           const int32_t *dst, int64_t B, const double *W, double *A, double *Bm, void *stream);
+int clane_pair_project_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                            const int32_t *dst, int64_t B, const float *W, float *A, float *Bm, void *stream);
+int clane_pair_loss_f32(const float *A, const float *Bm, int64_t B, int32_t d, const uint8_t *linked, const float *u,
+                        float *g, uint8_t *mask, double *ws, double *stats, void *stream);
+int clane_pair_loss_f64(const double *A, const double *Bm, int64_t B, int32_t d, const uint8_t *linked, const double *u,
+                        double *g, uint8_t *mask, double *ws, double *stats, void *stream);
+int64_t clane_pair_grad_ws_len(int64_t B, int32_t d);
+int clane_pair_grad_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                        const int32_t *dst, int64_t B, const float *A, const float *Bm, const float *g,
+                        const double *stats, float *ws, float *dW, void *stream);
+int clane_pair_grad_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                        const int32_t *dst, int64_t B, const double *A, const double *Bm, const double *g,
+                        const double *stats, double *ws, double *dW, void *stream);
+int clane_pair_grad_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *src,
+                         const int32_t *dst, int64_t B, const float *A, const float *Bm, const float *g,
+                         const double *stats, float *ws, float *dW, void *stream);
+int clane_adam_step_f32(float *W, float *m, float *v, const float *dW, int64_t n, double lr, const double *stats,
+                        double *state, void *stream);
+int clane_adam_step_f64(double *W, double *m, double *v, const double *dW, int64_t n, double lr, const double *stats,
+                        double *state, void *stream);
+int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, const int32_t *src,
+                      const int32_t *dst, int64_t B, uint8_t *linked, void *stream);
 
 #ifdef __cplusplus
 }
