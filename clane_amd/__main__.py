@@ -43,6 +43,11 @@ def _distributed_setup():
 
 
 def embedding(args):
+    predict_k = getattr(args, "predict_links", None)
+    if predict_k is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:       # before any work, as --train_similarity
+        raise NotImplementedError("--predict_links runs on one GPU only; several GPUs are out of scope")
+    if predict_k is None and getattr(args, "link_sources", None) is not None:
+        raise ValueError("--link_sources restricts --predict_links; give that flag too")
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
     say('[Embedding]', end='\n')
@@ -123,6 +128,13 @@ def embedding(args):
 
     say(f"The embeddings are stored in {args.output_root.joinpath('Z.npy').absolute()}.")
 
+    if predict_k is not None:
+        from .links import read_link_sources, write_links_tsv
+        sources = None if args.link_sources is None else read_link_sources(args.link_sources, g.vertex_ids)
+        ids, scores = g.predict_links(similarity_measure, k=predict_k, sources=sources)
+        n = write_links_tsv(args.output_root.joinpath('links.tsv'), g.vertex_ids, sources, ids, scores)
+        say(f"{n} predicted links are stored in {args.output_root.joinpath('links.tsv').absolute()}.")
+
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:
     Z = Z.cpu()
@@ -153,6 +165,14 @@ def get_parser():
                              "GPU, alternating with propagation (AlternatingEmbedder; the config's embedder keys are the "
                              "reference's: tolerence, tolerence_Z, tolerence_P, epoch, batch_size, lr).  One GPU only.  "
                              "Without the flag such a config ends as before: IterativeEmbedder is not implemented.")
+    parser.add_argument("--predict_links", type=int, default=None, metavar="K",
+                        help="(extension) after the embedding, write output_root/links.tsv: for every vertex the K (1..32) "
+                             "vertices it is most likely to link to under the configured similarity and does not link to "
+                             "yet, one 'src_id<TAB>dst_id<TAB>score' line per candidate, best first.  CosineSimilarity "
+                             "and AsymmertricSimilarity; one GPU only.")
+    parser.add_argument("--link_sources", type=Path, default=None, metavar="FILE",
+                        help="(extension) with --predict_links: a file of vertex ids, one per line -- rank links for these "
+                             "sources only, in the file's order.")
     parser.add_argument("--gpu", action='store_true')
     return parser
 

@@ -87,6 +87,13 @@ for _s in ("f32", "f64"):
     SIGNATURES[f"clane_pair_loss_{_s}"] = (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p])
     SIGNATURES[f"clane_adam_step_{_s}"] = (C.c_int, [_p, _p, _p, _p, _i64, C.c_double, _p, _p, _p])
 SIGNATURES["clane_pair_grad_ws_len"] = (_i64, [_i64, _i32])
+RANK_MAX_K = 32                     # CLANE_RANK_MAX_K
+for _s in ("f32", "f64", "bf16"):   # link prediction (csrc/link_rank.h)
+    SIGNATURES[f"clane_rank_scores_{_s}"] = (
+        C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p])
+    SIGNATURES[f"clane_pair_score_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p])
+for _s in ("f32", "f64"):
+    SIGNATURES[f"clane_rank_merge_{_s}"] = (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p])
 SIGNATURES["clane_pair_labels"] = (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p])
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
@@ -373,6 +380,21 @@ class KernelBackend(abc.ABC):
     def pair_labels(self, rowptr, colidx, nrows: int, src, dst, linked):
         """linked[k] = dst[k] is a column of row src[k] of a CSR with sorted, unique rows."""
         raise NotImplementedError(f"{type(self).__name__} has no pair_labels")
+
+    # link prediction (links.py): optional in the same way -- LinkRanker is the only caller.  Rows are TABLE ROWS (int32).
+    def rank_scores(self, S, N, table_rows: int, d: int, q_rows, mode: int, sums2, sq, label, excl_rowptr, excl_colidx,
+                    exclude_self: bool, k: int, n_slabs: int, cand_score, cand_id):
+        """The k best candidates of every query row in each of n_slabs ranges of the table: cand_score / cand_id
+        [Q, n_slabs, k], unused places -inf / -1."""
+        raise NotImplementedError(f"{type(self).__name__} has no rank_scores")
+
+    def rank_merge(self, cand_score, cand_id, n_slabs: int, k: int, out_score, out_id):
+        """[Q, n_slabs, k] candidates -> [Q, k], score descending, ties by id ascending."""
+        raise NotImplementedError(f"{type(self).__name__} has no rank_merge")
+
+    def pair_score(self, S, N, table_rows: int, d: int, src, dst, mode: int, sums2, sq, out):
+        """out[i] = score(src[i], dst[i]); an index outside the table reads as a zero row."""
+        raise NotImplementedError(f"{type(self).__name__} has no pair_score")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -748,6 +770,56 @@ class HipKernels(KernelBackend):
                      _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), nrows,
                      _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B,
                      _vec(linked, torch.uint8, "linked"), self._stream(linked))
+
+    # -- link prediction -----------------------------------------------------------------
+    @staticmethod
+    def _two_tables(S, N, table_rows: int, d: int, what: str):
+        sp, lds = _mat(S, "S")
+        np_, ldn = _mat(N, "N")
+        if S.dtype != N.dtype:
+            raise ValueError(f"{what}: S and N must share a dtype")
+        if S.shape[0] < table_rows or N.shape[0] < table_rows or S.shape[1] < d or N.shape[1] < d:
+            raise ValueError(f"{what}: S and N must hold at least {table_rows} rows of {d} columns")
+        return sp, lds, np_, ldn
+
+    def rank_scores(self, S, N, table_rows: int, d: int, q_rows, mode: int, sums2, sq, label, excl_rowptr, excl_colidx,
+                    exclude_self: bool, k: int, n_slabs: int, cand_score, cand_id):
+        sp, lds, np_, ldn = self._two_tables(S, N, table_rows, d, "rank_scores")
+        acc, Q = acc_dtype(S.dtype), q_rows.numel()
+        for t, n, name in ((sq, table_rows, "sq"), (label, table_rows, "label"), (excl_rowptr, table_rows + 1, "excl_rowptr")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"rank_scores: {name} needs {n} entries")
+        need = Q * max(int(n_slabs), 0) * max(int(k), 0)
+        if cand_score.numel() < need or cand_id.numel() < need:
+            raise ValueError("rank_scores: cand_score and cand_id need Q * n_slabs * k entries")
+        self._invoke(self._fn("clane_rank_scores", S.dtype), "clane_rank_scores",
+                     sp, lds, np_, ldn, table_rows, d, _vec(q_rows, torch.int32, "q_rows"), Q, mode, _ptr(sums2),
+                     None if sq is None else _vec(sq, acc, "sq"),
+                     None if label is None else _vec(label, torch.int32, "label"),
+                     None if excl_rowptr is None else _vec(excl_rowptr, torch.int64, "excl_rowptr"),
+                     None if excl_colidx is None else _vec(excl_colidx, torch.int32, "excl_colidx"),
+                     int(bool(exclude_self)), k, n_slabs, _vec(cand_score, acc, "cand_score"),
+                     _vec(cand_id, torch.int32, "cand_id"), self._stream(S))
+
+    def rank_merge(self, cand_score, cand_id, n_slabs: int, k: int, out_score, out_id):
+        Q = out_id.numel() // max(int(k), 1)
+        if out_score.numel() != out_id.numel() or cand_score.numel() < Q * n_slabs * k or cand_id.numel() < Q * n_slabs * k:
+            raise ValueError("rank_merge: out_* must be [Q, k] and cand_* [Q, n_slabs, k]")
+        self._invoke(self._fn("clane_rank_merge", cand_score.dtype), "clane_rank_merge",
+                     _vec(cand_score, cand_score.dtype, "cand_score"), _vec(cand_id, torch.int32, "cand_id"), Q, n_slabs,
+                     k, _vec(out_score, cand_score.dtype, "out_score"), _vec(out_id, torch.int32, "out_id"),
+                     self._stream(cand_score))
+
+    def pair_score(self, S, N, table_rows: int, d: int, src, dst, mode: int, sums2, sq, out):
+        sp, lds, np_, ldn = self._two_tables(S, N, table_rows, d, "pair_score")
+        acc = acc_dtype(S.dtype)
+        B = self._pairs(src, dst, "pair_score")
+        if out.numel() < B or (sq is not None and sq.numel() < table_rows):
+            raise ValueError("pair_score: out needs one entry per pair, sq one per table row")
+        self._invoke(self._fn("clane_pair_score", S.dtype), "clane_pair_score",
+                     sp, lds, np_, ldn, table_rows, d, _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B,
+                     mode, _ptr(sums2), None if sq is None else _vec(sq, acc, "sq"), _vec(out, acc, "out"),
+                     self._stream(S))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

@@ -11,8 +11,10 @@ from . import _hip
 from .plan import _round_up
 
 
-def build_P_bilinear(eng, W: torch.Tensor) -> None:
-    """``SweepEngine.build_P_bilinear``: P of the rows ``eng`` owns, from W = cat(Phi_src.weight, Phi_dst.weight)."""
+def project_table(eng, W: torch.Tensor):
+    """Y = Z W^T for EVERY row of ``eng``'s current table, into the engine's kept ``_Y`` buffer (allocated by the first
+    call): returns (Y[:, :d], Y[:, d:2d]) = (Phi_src z, Phi_dst z) per table row.  ``build_P_bilinear`` scores the edges
+    from them, ``LinkRanker`` (links.py) every pair."""
     if eng.columns:
         raise NotImplementedError(
             f"the bilinear similarity needs whole rows of Z; this engine divides the COLUMNS over the GPUs "
@@ -27,9 +29,15 @@ def build_P_bilinear(eng, W: torch.Tensor) -> None:
     if eng._Y is None:
         eng._Y = torch.empty(Z.shape[0], _round_up(2 * d, _hip.VEC_ELEMS[eng.acc_dtype]), dtype=eng.acc_dtype,
                              device=eng.device)
-    Y, kern = eng._Y, eng.k
-    kern.project_rows(Z, d, W, Y)
-    S, N = Y[:, :d], Y[:, d:2 * d]
+    Y = eng._Y
+    eng.k.project_rows(Z, d, W, Y)
+    return Y[:, :d], Y[:, d:2 * d]
+
+
+def build_P_bilinear(eng, W: torch.Tensor) -> None:
+    """``SweepEngine.build_P_bilinear``: P of the rows ``eng`` owns, from W = cat(Phi_src.weight, Phi_dst.weight)."""
+    S, N = project_table(eng, W)
+    d, kern = eng.d, eng.k
     if eng.E_loc > 0:
         for i, b in enumerate(eng.blocks):
             rp = eng.rowptr[b.local_start:]

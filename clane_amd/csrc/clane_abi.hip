@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "link_rank.h"
 #include "pair_train.h"
 #include "projection.h"
 #include "spmm_update.h"
@@ -631,6 +632,74 @@ int adam_step(A *W, A *m, A *v, const A *dW, int64_t n, double lr, const double 
     return check_launch("adam_step");
 }
 
+// ---- link prediction (link_rank.h) ---------------------------------------------------------------------------------
+inline bool score_mode_ok(int32_t mode) {
+    return mode == CLANE_SCORE_REFERENCE || mode == CLANE_SCORE_PER_EDGE || mode == CLANE_SCORE_RAW_DOT;
+}
+
+template <typename T, typename A>
+int rank_scores(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_rows, int32_t d, const int32_t *q_rows,
+                int64_t Q, int32_t mode, const double *sums2, const A *sq, const int32_t *label,
+                const int64_t *excl_rowptr, const int32_t *excl_colidx, int32_t exclude_self, int32_t k,
+                int32_t n_slabs, A *cand_score, int32_t *cand_id, void *stream) {
+    constexpr int MI = sizeof(A) == 8 ? 2 : 4;
+    static_assert(kRankMaxK == CLANE_RANK_MAX_K, "header and kernel disagree");
+    REQUIRE(d >= 1 && lds >= d && ldn >= d && Q >= 0 && table_rows >= 0 && table_rows <= INT32_MAX,
+            "rank_scores: bad shape rows=%lld Q=%lld d=%d lds=%lld ldn=%lld", (long long)table_rows, (long long)Q, d,
+            (long long)lds, (long long)ldn);
+    REQUIRE(k >= 1 && k <= CLANE_RANK_MAX_K, "rank_scores: k must be in [1, %d], got %d", CLANE_RANK_MAX_K, k);
+    REQUIRE(n_slabs >= 1, "rank_scores: n_slabs must be at least 1, got %d", n_slabs);
+    REQUIRE(score_mode_ok(mode), "rank_scores: unknown mode %d", mode);
+    REQUIRE(mode != CLANE_SCORE_REFERENCE || sums2, "rank_scores: mode REFERENCE needs sums2");
+    REQUIRE(mode != CLANE_SCORE_PER_EDGE || sq, "rank_scores: mode PER_EDGE needs sq");
+    REQUIRE((excl_rowptr == nullptr) == (excl_colidx == nullptr),
+            "rank_scores: excl_rowptr and excl_colidx come together or not at all");
+    if (Q == 0) return CLANE_OK;
+    REQUIRE(S && N && q_rows && cand_score && cand_id, "rank_scores: null pointer");
+    const int64_t q_tiles = ceil_div(Q, int64_t(32 * MI));
+    const int64_t blocks = q_tiles * n_slabs;
+    REQUIRE(blocks <= INT32_MAX, "rank_scores: %lld queries x %d slabs is too many for one launch", (long long)Q, n_slabs);
+    const int64_t tiles_total = ceil_div(table_rows, int64_t(kRankBN));
+    const int64_t tiles_per_slab = ceil_div(tiles_total > 0 ? tiles_total : 1, int64_t(n_slabs));
+    rank_scores_kernel<T, A, MI><<<unsigned(blocks), kBlock, rank_list_bytes<A>(32 * MI, k), (hipStream_t)stream>>>(
+        S, lds, N, ldn, table_rows, d, q_rows, Q, mode, sums2, sq, label, excl_rowptr, excl_colidx, exclude_self, k,
+        n_slabs, q_tiles, tiles_per_slab, cand_score, cand_id);
+    return check_launch("rank_scores");
+}
+
+template <typename A>
+int rank_merge(const A *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k, A *out_score,
+               int32_t *out_id, void *stream) {
+    REQUIRE(Q >= 0 && Q <= int64_t(INT32_MAX) * kWavesPerBlock, "rank_merge: bad shape Q=%lld", (long long)Q);
+    REQUIRE(k >= 1 && k <= CLANE_RANK_MAX_K, "rank_merge: k must be in [1, %d], got %d", CLANE_RANK_MAX_K, k);
+    REQUIRE(n_slabs >= 1, "rank_merge: n_slabs must be at least 1, got %d", n_slabs);
+    if (Q == 0) return CLANE_OK;
+    REQUIRE(cand_score && cand_id && out_score && out_id, "rank_merge: null pointer");
+    rank_merge_kernel<A><<<unsigned(ceil_div(Q, kWavesPerBlock)), kBlock, 0, (hipStream_t)stream>>>(
+        cand_score, cand_id, Q, n_slabs, k, out_score, out_id);
+    return check_launch("rank_merge");
+}
+
+template <typename T>
+int pair_score(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_rows, int32_t d, const int32_t *src,
+               const int32_t *dst, int64_t B, int32_t mode, const double *sums2, const typename Elem<T>::acc_t *sq,
+               typename Elem<T>::acc_t *out, void *stream) {
+    REQUIRE(d >= 1 && lds >= d && ldn >= d && B >= 0 && table_rows >= 0,
+            "pair_score: bad shape rows=%lld B=%lld d=%d lds=%lld ldn=%lld", (long long)table_rows, (long long)B, d,
+            (long long)lds, (long long)ldn);
+    REQUIRE(score_mode_ok(mode), "pair_score: unknown mode %d", mode);
+    REQUIRE(mode != CLANE_SCORE_REFERENCE || sums2, "pair_score: mode REFERENCE needs sums2");
+    REQUIRE(mode != CLANE_SCORE_PER_EDGE || sq, "pair_score: mode PER_EDGE needs sq");
+    if (B == 0) return CLANE_OK;
+    REQUIRE(S && N && src && dst && out, "pair_score: null pointer");
+    const Layout L = pick_layout<T>(d, {S, N}, {lds, ldn});
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
+        pair_score_kernel<T, VEC, LPR><<<grid_for_waves(ceil_div(B, kWave / LPR)), kBlock, 0, (hipStream_t)stream>>>(
+            S, lds, N, ldn, table_rows, d, src, dst, B, mode, sums2, sq, out);
+    });
+    return check_launch("pair_score");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -957,6 +1026,35 @@ int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrow
     pair_labels_kernel<<<grid_for_waves(ceil_div(B, kWave)), kBlock, 0, (hipStream_t)stream>>>(rowptr, colidx, nrows,
                                                                                               src, dst, B, linked);
     return check_launch("pair_labels");
+}
+
+#define CLANE_LINK_WRAPPERS(SUF, CT, T, AT)                                                                            \
+    int clane_rank_scores_##SUF(const CT *S, int64_t lds, const CT *N, int64_t ldn, int64_t table_rows, int32_t d,    \
+                                const int32_t *q_rows, int64_t Q, int32_t mode, const double *sums2, const AT *sq,    \
+                                const int32_t *label, const int64_t *excl_rowptr, const int32_t *excl_colidx,         \
+                                int32_t exclude_self, int32_t k, int32_t n_slabs, AT *cand_score, int32_t *cand_id,   \
+                                void *stream) {                                                                       \
+        return rank_scores<T, AT>(reinterpret_cast<const T *>(S), lds, reinterpret_cast<const T *>(N), ldn,           \
+                                  table_rows, d, q_rows, Q, mode, sums2, sq, label, excl_rowptr, excl_colidx,         \
+                                  exclude_self, k, n_slabs, cand_score, cand_id, stream);                             \
+    }                                                                                                                 \
+    int clane_pair_score_##SUF(const CT *S, int64_t lds, const CT *N, int64_t ldn, int64_t table_rows, int32_t d,     \
+                               const int32_t *src, const int32_t *dst, int64_t B, int32_t mode, const double *sums2,  \
+                               const AT *sq, AT *out, void *stream) {                                                 \
+        return pair_score<T>(reinterpret_cast<const T *>(S), lds, reinterpret_cast<const T *>(N), ldn, table_rows, d, \
+                             src, dst, B, mode, sums2, sq, out, stream);                                              \
+    }
+CLANE_LINK_WRAPPERS(f32, float, float, float)
+CLANE_LINK_WRAPPERS(f64, double, double, double)
+CLANE_LINK_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_LINK_WRAPPERS
+int clane_rank_merge_f32(const float *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k,
+                         float *out_score, int32_t *out_id, void *stream) {
+    return rank_merge<float>(cand_score, cand_id, Q, n_slabs, k, out_score, out_id, stream);
+}
+int clane_rank_merge_f64(const double *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k,
+                         double *out_score, int32_t *out_id, void *stream) {
+    return rank_merge<double>(cand_score, cand_id, Q, n_slabs, k, out_score, out_id, stream);
 }
 
 }  // extern "C"

@@ -471,6 +471,26 @@ class Graph(torch.utils.data.Dataset):
         values = self._gather_P(eng)
         return torch.sparse_coo_tensor(self._edge_index(), values, size=(len(self), len(self)), is_coalesced=True)
 
+    def predict_links(self, similarity, k: int = 10, sources=None, exclude_existing: bool = True):
+        """(ids [Q, k] int64, scores [Q, k]) as host tensors (extension; the reference stops at Z): for every source
+        vertex index (None: all vertices, in order) the ``k`` vertices it is most likely to link to under ``similarity``
+        and the CURRENT embeddings, best first, ties by vertex index; itself never, its existing out-neighbours unless
+        ``exclude_existing`` is off; places beyond the eligible vertices hold -1 / -inf.  ``CosineSimilarity`` (its
+        ``mode``) and ``AsymmertricSimilarity`` (its current weights) are scored on the GPU against all vertices at once
+        (links.py); any other callable raises NotImplementedError.  One GPU only."""
+        from .links import SUPPORTED, LinkRanker
+        from .similarity import AsymmertricSimilarity, CosineSimilarity
+        if isinstance(similarity, CosineSimilarity):
+            eng = self.engine(cosine_mode=similarity.mode)
+        elif isinstance(similarity, AsymmertricSimilarity):
+            eng = self.engine()
+        else:
+            raise NotImplementedError(
+                f"predict_links scores with {SUPPORTED}; a plug-in similarity ({type(similarity).__name__}) has no "
+                f"kernel to score all pairs with")
+        ids, scores = LinkRanker(eng, similarity).top_k(k, sources, exclude_existing)
+        return ids.cpu(), scores.cpu()
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

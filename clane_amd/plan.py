@@ -91,3 +91,22 @@ def column_slice(d: int, dtype: torch.dtype, world: int, rank: int):
     p0 = rank * base + min(rank, rem)
     p1 = p0 + base + (1 if rank < rem else 0)
     return min(d, p0 * vec), min(d, p1 * vec)
+
+
+# Link ranking (csrc/link_rank.h): a workgroup owns one tile of RANK_QUERY_TILE queries (64 in fp64) and one slab of the
+# candidate rows, so a small query batch alone would leave most of the 256 CUs idle.  The candidate rows are cut into
+# enough slabs for RANK_WORKGROUPS_PER_CU workgroups per CU (two are resident per CU: one to run, one to take over, and
+# a tail of whole waves of workgroups), never more slabs than the table has RANK_CANDIDATE_TILE-row tiles (a slab
+# without a tile is an idle workgroup) and never fewer than one.  Results do not depend on the choice.
+RANK_QUERY_TILE = 128
+RANK_CANDIDATE_TILE = 128
+RANK_WORKGROUPS_PER_CU = 4
+COMPUTE_UNITS = 256
+
+
+def rank_slabs(n_queries: int, table_rows: int, query_tile: int = RANK_QUERY_TILE) -> int:
+    """n_slabs of a rank_scores call over ``n_queries`` queries and ``table_rows`` candidate rows."""
+    q_tiles = max(1, -(-int(n_queries) // query_tile))
+    tiles = max(1, -(-int(table_rows) // RANK_CANDIDATE_TILE))
+    want = -(-RANK_WORKGROUPS_PER_CU * COMPUTE_UNITS // q_tiles)
+    return max(1, min(want, tiles))

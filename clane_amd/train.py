@@ -29,6 +29,29 @@ def rows_of_vertices(eng, vertices) -> torch.Tensor:
     return eng.pos[v].to(torch.int32)
 
 
+def sorted_adjacency(eng):
+    """(rowptr int64 [R + 1], colidx int32, R): the adjacency in TABLE-ROW numbering with every row sorted by column --
+    what ``clane_pair_labels`` and the exclusion of ``clane_rank_scores_*`` search.  The engine's own CSR keeps the edges
+    of its class rows in (class of the column, column) order, so the adjacency is sorted once more; built once per
+    engine and shared by ``PairSampler`` and ``LinkRanker`` (the graph of an engine never changes)."""
+    cached = getattr(eng, "_sorted_adjacency", None)
+    if cached is not None:
+        return cached
+    dev = eng.device
+    R = eng.part.padded_vertices
+    own = torch.from_numpy(eng.part.local_positions()).to(dev)
+    deg = (eng.rowptr[1:] - eng.rowptr[:-1])[:eng.part.n_local]
+    src = torch.repeat_interleave(own[:deg.numel()], deg)
+    key = torch.sort(src * R + eng.colidx[:eng.E_loc].long()).values
+    counts = torch.zeros(R, dtype=torch.int64, device=dev)
+    counts.index_add_(0, src, torch.ones_like(src))
+    rowptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(counts, 0)
+    colidx = (key % R).to(torch.int32) if key.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+    eng._sorted_adjacency = (rowptr, colidx, R)
+    return eng._sorted_adjacency
+
+
 class SimilarityTrainer:
     """W = cat(Phi_src.weight, Phi_dst.weight) [2d, d], Adam's m and v, the step counter and the epoch-loss accumulator
     on the device, with the buffers of one batch of up to ``batch_size`` pairs (``SweepEngine.similarity_trainer``)."""
@@ -96,20 +119,7 @@ class PairSampler:
             raise ValueError("PairSampler: positive_fraction must be in [0, 1]")
         self.eng, self.batch_size, self.gen, self.positive_fraction = engine, int(batch_size), generator, float(positive_fraction)
         self.n_batches = engine.V // self.batch_size
-        # the engine's CSR keeps the edges of its class rows in (class of the column, column) order: the labels need rows
-        # sorted by column, so the adjacency is sorted once more, in table-row numbering, for the binary search
-        eng, dev = engine, engine.device
-        R = eng.part.padded_vertices
-        own = torch.from_numpy(eng.part.local_positions()).to(dev)
-        deg = (eng.rowptr[1:] - eng.rowptr[:-1])[:eng.part.n_local]
-        src = torch.repeat_interleave(own[:deg.numel()], deg)
-        key = torch.sort(src * R + eng.colidx[:eng.E_loc].long()).values
-        counts = torch.zeros(R, dtype=torch.int64, device=dev)
-        counts.index_add_(0, src, torch.ones_like(src))
-        self.rowptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-        self.rowptr[1:] = torch.cumsum(counts, 0)
-        self.colidx = (key % R).to(torch.int32) if key.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
-        self.nrows = R
+        self.rowptr, self.colidx, self.nrows = sorted_adjacency(engine)
 
     def _rand(self, n: int) -> torch.Tensor:
         return torch.rand(n, generator=self.gen, device=self.gen.device, dtype=torch.float64).to(self.eng.device)

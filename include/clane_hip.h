@@ -48,7 +48,9 @@ extern "C" {
                              *    similarity: AsymmertricSimilarity's P without a per-edge projection)
                              * 5, additions that change no existing call (the number stays: every v5 caller keeps working):
                              *    + clane_pair_project_*, clane_pair_loss_*, clane_pair_grad_*, clane_pair_grad_ws_len,
-                             *    clane_adam_step_*, clane_pair_labels (training the bilinear similarity on the device) */
+                             *    clane_adam_step_*, clane_pair_labels (training the bilinear similarity on the device)
+                             *    + clane_rank_scores_*, clane_rank_merge_*, clane_pair_score_* (link prediction: top-k
+                             *    candidates of query rows against the whole table, scores of explicit pairs) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -453,6 +455,65 @@ int clane_adam_step_f64(double *W, double *m, double *v, const double *dW, int64
                         double *state, void *stream);
 int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrows, const int32_t *src,
                       const int32_t *dst, int64_t B, uint8_t *linked, void *stream);
+
+/* ---- Link prediction: which rows does a query row score highest against, and what does an explicit pair score.  No
+ * reference counterpart (the reference stops at Z.npy); the score is the model's own: the bilinear
+ * (Phi_src z_u) . (Phi_dst z_v) of AsymmertricSimilarity (similarity.py:40-57) or the cosine of CosineSimilarity
+ * (similarity.py:26-37).  S (leading dimension lds) is the query table, N (ldn) the candidate table, both of
+ * table_rows rows of type T; only columns [0, d) are read.  Bilinear: S = Y, N = Y + d, lds = ldn = ldy of the table
+ * clane_project_rows_* leaves (f32 / f64 instance).  Cosine: S = N = Z.  mode / sums2 / sq exactly as
+ * clane_edge_score_* takes them, sq indexed by table row: RAW_DOT the dot; PER_EDGE dot / (sqrt(sq[q]) sqrt(sq[v])),
+ * 0 where sq[q] sq[v] == 0; REFERENCE dot / sqrt(sums2[0] sums2[1]).  Inputs are assumed finite.  No allocation, no
+ * synchronisation, no atomics on memory; two calls give the same bits.
+ *
+ *  clane_rank_scores_* : for query i = row q_rows[i] (int32, repeats allowed; a row outside the table has no
+ *                        candidates) the k best candidates of every one of n_slabs contiguous ranges of the table's
+ *                        rows: cand_score (accumulate dtype) and cand_id (int32), both [Q, n_slabs, k], unused places
+ *                        -inf / -1.  The Q x table_rows scores never exist in memory: the MFMA tiling of
+ *                        clane_project_rows_* with the query rows gathered, the selection fused behind each tile.
+ *                        label (int32 [table_rows], NULL = the row itself): the id reported for a candidate and the
+ *                        key that breaks ties; label[v] < 0: row v never is a candidate (padding rows).
+ *                        excl_rowptr (int64 [table_rows + 1]) / excl_colidx (int32): a CSR in table-row numbering with
+ *                        sorted, unique rows (what clane_pair_labels searches); candidate v is skipped for query row r
+ *                        when v is in row r.  Both NULL: nothing is skipped this way.  exclude_self != 0 also skips
+ *                        v == r.  k in 1..CLANE_RANK_MAX_K.  n_slabs >= 1 lets a small Q fill the card; more slabs
+ *                        than the table has 128-row tiles leave the surplus empty.
+ *  clane_rank_merge_*  : out_score / out_id [Q, k] from the [Q, n_slabs, k] candidates, score descending, ties by
+ *                        label ascending -- a total order, labels being unique among eligible rows; fewer than k
+ *                        eligible candidates: the tail is -inf / -1.  A pair's score comes out of the same accumulation
+ *                        chain whatever slab it falls in: the result is bit-identical for every n_slabs.
+ *  clane_pair_score_*  : out[i] = score(src[i], dst[i]) for B explicit pairs of table rows (int32; an index outside
+ *                        [0, table_rows) reads as a zero row: score 0) -- held-out evaluation touches nothing of the
+ *                        size of the table.  The lane layout of clane_edge_score_* (a sub-wave per pair). */
+#define CLANE_RANK_MAX_K 32
+int clane_rank_scores_f32(const float *S, int64_t lds, const float *N, int64_t ldn, int64_t table_rows, int32_t d,
+                          const int32_t *q_rows, int64_t Q, int32_t mode, const double *sums2, const float *sq,
+                          const int32_t *label, const int64_t *excl_rowptr, const int32_t *excl_colidx,
+                          int32_t exclude_self, int32_t k, int32_t n_slabs, float *cand_score, int32_t *cand_id,
+                          void *stream);
+int clane_rank_scores_f64(const double *S, int64_t lds, const double *N, int64_t ldn, int64_t table_rows, int32_t d,
+                          const int32_t *q_rows, int64_t Q, int32_t mode, const double *sums2, const double *sq,
+                          const int32_t *label, const int64_t *excl_rowptr, const int32_t *excl_colidx,
+                          int32_t exclude_self, int32_t k, int32_t n_slabs, double *cand_score, int32_t *cand_id,
+                          void *stream);
+int clane_rank_scores_bf16(const uint16_t *S, int64_t lds, const uint16_t *N, int64_t ldn, int64_t table_rows,
+                           int32_t d, const int32_t *q_rows, int64_t Q, int32_t mode, const double *sums2,
+                           const float *sq, const int32_t *label, const int64_t *excl_rowptr,
+                           const int32_t *excl_colidx, int32_t exclude_self, int32_t k, int32_t n_slabs,
+                           float *cand_score, int32_t *cand_id, void *stream);
+int clane_rank_merge_f32(const float *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k,
+                         float *out_score, int32_t *out_id, void *stream);
+int clane_rank_merge_f64(const double *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k,
+                         double *out_score, int32_t *out_id, void *stream);
+int clane_pair_score_f32(const float *S, int64_t lds, const float *N, int64_t ldn, int64_t table_rows, int32_t d,
+                         const int32_t *src, const int32_t *dst, int64_t B, int32_t mode, const double *sums2,
+                         const float *sq, float *out, void *stream);
+int clane_pair_score_f64(const double *S, int64_t lds, const double *N, int64_t ldn, int64_t table_rows, int32_t d,
+                         const int32_t *src, const int32_t *dst, int64_t B, int32_t mode, const double *sums2,
+                         const double *sq, double *out, void *stream);
+int clane_pair_score_bf16(const uint16_t *S, int64_t lds, const uint16_t *N, int64_t ldn, int64_t table_rows,
+                          int32_t d, const int32_t *src, const int32_t *dst, int64_t B, int32_t mode,
+                          const double *sums2, const float *sq, float *out, void *stream);
 
 #ifdef __cplusplus
 }
