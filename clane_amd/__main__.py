@@ -48,15 +48,22 @@ def embedding(args):
         raise NotImplementedError("--predict_links runs on one GPU only; several GPUs are out of scope")
     if predict_k is None and getattr(args, "link_sources", None) is not None:
         raise ValueError("--link_sources restricts --predict_links; give that flag too")
-    rank, world = _distributed_setup()
-    say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
-    say('[Embedding]', end='\n')
-
     if args.config_file.absolute().exists():
         with open(args.config_file.absolute(), 'r') as config_io:
             hparams = yaml.load(config_io, Loader=yaml.FullLoader)
     else:
         raise FileNotFoundError(f"Config file not found. {args.config_file.absolute()}")
+    # optional section (extension): link_evaluation: {pairs: held_out.tsv, hits: [1, 3, 10], filter_existing: true}
+    link_eval = hparams.get("link_evaluation") if isinstance(hparams, dict) else None
+    if link_eval is not None:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                    # before any work, as --predict_links
+            raise NotImplementedError("link_evaluation runs on one GPU only; several GPUs are out of scope")
+        if not isinstance(link_eval, dict) or "pairs" not in link_eval:
+            raise ValueError("link_evaluation: the section needs 'pairs', the file of held-out src<TAB>dst lines")
+
+    rank, world = _distributed_setup()
+    say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
+    say('[Embedding]', end='\n')
 
     device = torch.device('cuda') if args.gpu else torch.device('cpu')
     g = Graph(data_root=args.data_root, **hparams["graph"])
@@ -134,6 +141,22 @@ def embedding(args):
         ids, scores = g.predict_links(similarity_measure, k=predict_k, sources=sources)
         n = write_links_tsv(args.output_root.joinpath('links.tsv'), g.vertex_ids, sources, ids, scores)
         say(f"{n} predicted links are stored in {args.output_root.joinpath('links.tsv').absolute()}.")
+
+    if link_eval is not None:                       # with the similarity the run ends with: trained weights included
+        import json
+        from .links import read_link_pairs
+        pairs_file = Path(link_eval["pairs"])
+        if not pairs_file.is_absolute():
+            pairs_file = Path(args.data_root) / pairs_file
+        src, dst = read_link_pairs(pairs_file, g.vertex_ids)
+        filtered = bool(link_eval.get("filter_existing", True))
+        metrics = g.evaluate_links(similarity_measure, src, dst, hits=tuple(link_eval.get("hits", (1, 3, 10))),
+                                   filter_existing=filtered)
+        out = args.output_root.joinpath('link_metrics.json')
+        with open(out, "w") as io:
+            json.dump({**metrics, "similarity": type(similarity_measure).__name__, "filtered": filtered}, io, indent=1)
+            io.write("\n")
+        say(f"The link metrics of {metrics['pairs']} held-out pairs are stored in {out.absolute()}.")
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

@@ -92,6 +92,8 @@ for _s in ("f32", "f64", "bf16"):   # link prediction (csrc/link_rank.h)
     SIGNATURES[f"clane_rank_scores_{_s}"] = (
         C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p])
     SIGNATURES[f"clane_pair_score_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p])
+    SIGNATURES[f"clane_rank_count_{_s}"] = (      # held-out link evaluation (csrc/link_eval.h)
+        C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p])
 for _s in ("f32", "f64"):
     SIGNATURES[f"clane_rank_merge_{_s}"] = (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p])
 SIGNATURES["clane_pair_labels"] = (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p])
@@ -395,6 +397,13 @@ class KernelBackend(abc.ABC):
     def pair_score(self, S, N, table_rows: int, d: int, src, dst, mode: int, sums2, sq, out):
         """out[i] = score(src[i], dst[i]); an index outside the table reads as a zero row."""
         raise NotImplementedError(f"{type(self).__name__} has no pair_score")
+
+    def rank_count(self, S, N, table_rows: int, d: int, q_rows, t_rows, mode: int, sums2, sq, label, excl_rowptr,
+                   excl_colidx, exclude_self: bool, n_slabs: int, target_score, counts):
+        """For pair i = (q_rows[i], t_rows[i]): target_score[i], the pair's score as rank_scores computes it, and counts
+        [B, n_slabs, 4] = (greater, equal_lower, equal_higher, eligible) among each slab's candidates; a pair without a
+        rank: -1 / -inf."""
+        raise NotImplementedError(f"{type(self).__name__} has no rank_count")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -820,6 +829,26 @@ class HipKernels(KernelBackend):
                      sp, lds, np_, ldn, table_rows, d, _vec(src, torch.int32, "src"), _vec(dst, torch.int32, "dst"), B,
                      mode, _ptr(sums2), None if sq is None else _vec(sq, acc, "sq"), _vec(out, acc, "out"),
                      self._stream(S))
+
+    def rank_count(self, S, N, table_rows: int, d: int, q_rows, t_rows, mode: int, sums2, sq, label, excl_rowptr,
+                   excl_colidx, exclude_self: bool, n_slabs: int, target_score, counts):
+        sp, lds, np_, ldn = self._two_tables(S, N, table_rows, d, "rank_count")
+        acc = acc_dtype(S.dtype)
+        B = self._pairs(q_rows, t_rows, "rank_count")
+        for t, n, name in ((sq, table_rows, "sq"), (label, table_rows, "label"), (excl_rowptr, table_rows + 1, "excl_rowptr")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"rank_count: {name} needs {n} entries")
+        if target_score.numel() < B or counts.numel() < B * max(int(n_slabs), 0) * 4:
+            raise ValueError("rank_count: target_score needs B entries and counts B * n_slabs * 4")
+        self._invoke(self._fn("clane_rank_count", S.dtype), "clane_rank_count",
+                     sp, lds, np_, ldn, table_rows, d, _vec(q_rows, torch.int32, "q_rows"),
+                     _vec(t_rows, torch.int32, "t_rows"), B, mode, _ptr(sums2),
+                     None if sq is None else _vec(sq, acc, "sq"),
+                     None if label is None else _vec(label, torch.int32, "label"),
+                     None if excl_rowptr is None else _vec(excl_rowptr, torch.int64, "excl_rowptr"),
+                     None if excl_colidx is None else _vec(excl_colidx, torch.int32, "excl_colidx"),
+                     int(bool(exclude_self)), n_slabs, _vec(target_score, acc, "target_score"),
+                     _vec(counts, torch.int32, "counts"), self._stream(S))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

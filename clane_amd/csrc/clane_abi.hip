@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "link_eval.h"
 #include "link_rank.h"
 #include "pair_train.h"
 #include "projection.h"
@@ -667,6 +668,34 @@ int rank_scores(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_
     return check_launch("rank_scores");
 }
 
+template <typename T, typename A>
+int rank_count(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_rows, int32_t d, const int32_t *q_rows,
+               const int32_t *t_rows, int64_t B, int32_t mode, const double *sums2, const A *sq, const int32_t *label,
+               const int64_t *excl_rowptr, const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs,
+               A *target_score, int32_t *counts, void *stream) {
+    constexpr int MI = sizeof(A) == 8 ? 2 : 4;
+    REQUIRE(d >= 1 && lds >= d && ldn >= d && B >= 0 && table_rows >= 0 && table_rows <= INT32_MAX,
+            "rank_count: bad shape rows=%lld B=%lld d=%d lds=%lld ldn=%lld", (long long)table_rows, (long long)B, d,
+            (long long)lds, (long long)ldn);
+    REQUIRE(n_slabs >= 1, "rank_count: n_slabs must be at least 1, got %d", n_slabs);
+    REQUIRE(score_mode_ok(mode), "rank_count: unknown mode %d", mode);
+    REQUIRE(mode != CLANE_SCORE_REFERENCE || sums2, "rank_count: mode REFERENCE needs sums2");
+    REQUIRE(mode != CLANE_SCORE_PER_EDGE || sq, "rank_count: mode PER_EDGE needs sq");
+    REQUIRE((excl_rowptr == nullptr) == (excl_colidx == nullptr),
+            "rank_count: excl_rowptr and excl_colidx come together or not at all");
+    if (B == 0) return CLANE_OK;
+    REQUIRE(S && N && q_rows && t_rows && target_score && counts, "rank_count: null pointer");
+    const int64_t q_tiles = ceil_div(B, int64_t(32 * MI));
+    const int64_t blocks = q_tiles * n_slabs;
+    REQUIRE(blocks <= INT32_MAX, "rank_count: %lld pairs x %d slabs is too many for one launch", (long long)B, n_slabs);
+    const int64_t tiles_total = ceil_div(table_rows, int64_t(kRankBN));
+    const int64_t tiles_per_slab = ceil_div(tiles_total > 0 ? tiles_total : 1, int64_t(n_slabs));
+    rank_count_kernel<T, A, MI><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(
+        S, lds, N, ldn, table_rows, d, q_rows, t_rows, B, mode, sums2, sq, label, excl_rowptr, excl_colidx, exclude_self,
+        n_slabs, q_tiles, tiles_per_slab, target_score, counts);
+    return check_launch("rank_count");
+}
+
 template <typename A>
 int rank_merge(const A *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k, A *out_score,
                int32_t *out_id, void *stream) {
@@ -1037,6 +1066,15 @@ int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrow
         return rank_scores<T, AT>(reinterpret_cast<const T *>(S), lds, reinterpret_cast<const T *>(N), ldn,           \
                                   table_rows, d, q_rows, Q, mode, sums2, sq, label, excl_rowptr, excl_colidx,         \
                                   exclude_self, k, n_slabs, cand_score, cand_id, stream);                             \
+    }                                                                                                                 \
+    int clane_rank_count_##SUF(const CT *S, int64_t lds, const CT *N, int64_t ldn, int64_t table_rows, int32_t d,     \
+                               const int32_t *q_rows, const int32_t *t_rows, int64_t B, int32_t mode,                 \
+                               const double *sums2, const AT *sq, const int32_t *label, const int64_t *excl_rowptr,   \
+                               const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs, AT *target_score,   \
+                               int32_t *counts, void *stream) {                                                       \
+        return rank_count<T, AT>(reinterpret_cast<const T *>(S), lds, reinterpret_cast<const T *>(N), ldn,            \
+                                 table_rows, d, q_rows, t_rows, B, mode, sums2, sq, label, excl_rowptr, excl_colidx,  \
+                                 exclude_self, n_slabs, target_score, counts, stream);                                \
     }                                                                                                                 \
     int clane_pair_score_##SUF(const CT *S, int64_t lds, const CT *N, int64_t ldn, int64_t table_rows, int32_t d,     \
                                const int32_t *src, const int32_t *dst, int64_t B, int32_t mode, const double *sums2,  \

@@ -491,6 +491,24 @@ class Graph(torch.utils.data.Dataset):
         ids, scores = LinkRanker(eng, similarity).top_k(k, sources, exclude_existing)
         return ids.cpu(), scores.cpu()
 
+    def evaluate_links(self, similarity, src, dst, hits=(1, 3, 10), filter_existing: bool = True) -> dict:
+        """How well ``similarity`` and the CURRENT embeddings predict the held-out pairs (src[i], dst[i]) of vertex indices
+        (extension): the exact rank of dst[i] among all vertices src[i] does not link to yet (``filter_existing``; itself
+        and dst[i] never count), and from the ranks ``{"pairs", "skipped", "mrr", "mean_rank", "hits": {K: ..}, "auc"}``
+        (links.LinkMetrics.as_dict) on the host.  Similarities and engines as ``predict_links``: any other callable,
+        several GPUs and a column division raise NotImplementedError."""
+        from .links import SUPPORTED, LinkRanker
+        from .similarity import AsymmertricSimilarity, CosineSimilarity
+        if isinstance(similarity, CosineSimilarity):
+            eng = self.engine(cosine_mode=similarity.mode)
+        elif isinstance(similarity, AsymmertricSimilarity):
+            eng = self.engine()
+        else:
+            raise NotImplementedError(
+                f"evaluate_links scores with {SUPPORTED}; a plug-in similarity ({type(similarity).__name__}) has no "
+                f"kernel to score all pairs with")
+        return LinkRanker(eng, similarity).evaluate(src, dst, hits, filter_existing).as_dict()
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

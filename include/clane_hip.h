@@ -50,7 +50,9 @@ extern "C" {
                              *    + clane_pair_project_*, clane_pair_loss_*, clane_pair_grad_*, clane_pair_grad_ws_len,
                              *    clane_adam_step_*, clane_pair_labels (training the bilinear similarity on the device)
                              *    + clane_rank_scores_*, clane_rank_merge_*, clane_pair_score_* (link prediction: top-k
-                             *    candidates of query rows against the whole table, scores of explicit pairs) */
+                             *    candidates of query rows against the whole table, scores of explicit pairs)
+                             *    + clane_rank_count_* (held-out link evaluation: a pair's score and how many eligible rows of
+                             *    the whole table score above it or tie with it -- the filtered rank without a score matrix) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -484,7 +486,22 @@ int clane_pair_labels(const int64_t *rowptr, const int32_t *colidx, int64_t nrow
  *                        chain whatever slab it falls in: the result is bit-identical for every n_slabs.
  *  clane_pair_score_*  : out[i] = score(src[i], dst[i]) for B explicit pairs of table rows (int32; an index outside
  *                        [0, table_rows) reads as a zero row: score 0) -- held-out evaluation touches nothing of the
- *                        size of the table.  The lane layout of clane_edge_score_* (a sub-wave per pair). */
+ *                        size of the table.  The lane layout of clane_edge_score_* (a sub-wave per pair).
+ *  clane_rank_count_*  : for pair i = (query row q_rows[i], target row t_rows[i]) (int32, repeats allowed) the filtered
+ *                        rank's ingredients.  target_score[B] (accumulate dtype) is the score the pair gets INSIDE
+ *                        clane_rank_scores_* -- the same accumulation chain and scaling, bit for bit.  counts
+ *                        [B, n_slabs, 4] (int32) holds for the candidate rows of slab s, in this order: greater (eligible
+ *                        candidates that score above the target), equal_lower / equal_higher (eligible candidates whose
+ *                        score equals the target's and whose label is below / above the target's) and eligible (all
+ *                        eligible candidates).  The caller sums over the slabs (integers: the sums do not depend on
+ *                        n_slabs); 1 + greater + equal_lower is the target's place in the order of clane_rank_merge_*.
+ *                        Candidate v is eligible for the pair under the rules of clane_rank_scores_* (label, excl_*,
+ *                        exclude_self, all taken the same way) and when it is not the target itself: the target never
+ *                        is a candidate and never is filtered -- a target inside the query's exclusion row (an edge
+ *                        still in the graph) is ranked among the non-edges.  A pair whose query or target lies outside
+ *                        the table, or whose target has a negative label, has no rank: four -1 in every slab and -inf in
+ *                        target_score.  The exclusion rows are walked by a cursor per pair, not searched per candidate.
+ *                        No atomics on memory; two calls give the same bits. */
 #define CLANE_RANK_MAX_K 32
 int clane_rank_scores_f32(const float *S, int64_t lds, const float *N, int64_t ldn, int64_t table_rows, int32_t d,
                           const int32_t *q_rows, int64_t Q, int32_t mode, const double *sums2, const float *sq,
@@ -514,6 +531,21 @@ int clane_pair_score_f64(const double *S, int64_t lds, const double *N, int64_t 
 int clane_pair_score_bf16(const uint16_t *S, int64_t lds, const uint16_t *N, int64_t ldn, int64_t table_rows,
                           int32_t d, const int32_t *src, const int32_t *dst, int64_t B, int32_t mode,
                           const double *sums2, const float *sq, float *out, void *stream);
+int clane_rank_count_f32(const float *S, int64_t lds, const float *N, int64_t ldn, int64_t table_rows, int32_t d,
+                         const int32_t *q_rows, const int32_t *t_rows, int64_t B, int32_t mode, const double *sums2,
+                         const float *sq, const int32_t *label, const int64_t *excl_rowptr,
+                         const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs, float *target_score,
+                         int32_t *counts, void *stream);
+int clane_rank_count_f64(const double *S, int64_t lds, const double *N, int64_t ldn, int64_t table_rows, int32_t d,
+                         const int32_t *q_rows, const int32_t *t_rows, int64_t B, int32_t mode, const double *sums2,
+                         const double *sq, const int32_t *label, const int64_t *excl_rowptr,
+                         const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs, double *target_score,
+                         int32_t *counts, void *stream);
+int clane_rank_count_bf16(const uint16_t *S, int64_t lds, const uint16_t *N, int64_t ldn, int64_t table_rows, int32_t d,
+                         const int32_t *q_rows, const int32_t *t_rows, int64_t B, int32_t mode, const double *sums2,
+                         const float *sq, const int32_t *label, const int64_t *excl_rowptr,
+                         const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs, float *target_score,
+                         int32_t *counts, void *stream);
 
 #ifdef __cplusplus
 }
