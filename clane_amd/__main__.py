@@ -60,6 +60,13 @@ def embedding(args):
             raise NotImplementedError("link_evaluation runs on one GPU only; several GPUs are out of scope")
         if not isinstance(link_eval, dict) or "pairs" not in link_eval:
             raise ValueError("link_evaluation: the section needs 'pairs', the file of held-out src<TAB>dst lines")
+    # optional section (extension): node_classification: {labels: Y, ratios: [..], runs: 10, seed: 0, l2: 1.0, baseline: true}
+    node_cls = hparams.get("node_classification") if isinstance(hparams, dict) else None
+    if node_cls is not None:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                    # before any work, as link_evaluation
+            raise NotImplementedError("node_classification runs on one GPU only; several GPUs are out of scope")
+        if not isinstance(node_cls, dict) or "labels" not in node_cls:
+            raise ValueError("node_classification: the section needs 'labels', the file of id<TAB>class lines")
 
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
@@ -157,6 +164,26 @@ def embedding(args):
             json.dump({**metrics, "similarity": type(similarity_measure).__name__, "filtered": filtered}, io, indent=1)
             io.write("\n")
         say(f"The link metrics of {metrics['pairs']} held-out pairs are stored in {out.absolute()}.")
+
+    if node_cls is not None:                        # the README's experiment on the embeddings the run ends with
+        import json
+        labels_file = Path(node_cls["labels"])
+        if not labels_file.is_absolute():
+            labels_file = Path(args.data_root) / labels_file
+        kw = {key: node_cls[key] for key in ("ratios", "runs", "seed", "l2") if key in node_cls}
+        tables = {"Z": g.evaluate_labels(labels_file, table="Z", **kw)}
+        if node_cls.get("baseline", False):
+            tables["X"] = g.evaluate_labels(labels_file, table="X", **kw)
+        first = tables["Z"]
+        out = args.output_root.joinpath('label_metrics.json')
+        with open(out, "w") as io:
+            json.dump({"labels": str(labels_file), "labelled": first["labelled"], "class_names": first["class_names"],
+                       "ratios": [r["ratio"] for r in first["rows"]], "runs": first["runs"], "seed": first["seed"],
+                       "l2": first["l2"],
+                       "tables": {name: {"rows": t["rows"], "fits": t["fits"], "skipped_fits": t["skipped_fits"]}
+                                  for name, t in tables.items()}}, io, indent=1)
+            io.write("\n")
+        say(f"The F1 table of {first['labelled']} labelled vertices is stored in {out.absolute()}.")
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

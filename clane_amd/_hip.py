@@ -97,6 +97,21 @@ for _s in ("f32", "f64", "bf16"):   # link prediction (csrc/link_rank.h)
 for _s in ("f32", "f64"):
     SIGNATURES[f"clane_rank_merge_{_s}"] = (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p])
 SIGNATURES["clane_pair_labels"] = (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p])
+PROBE_MAX_CLASSES = 64              # CLANE_PROBE_MAX_CLASSES
+PROBE_WRITE_G, PROBE_WRITE_PRED = 1, 2
+for _s in ("f32", "f64", "bf16"):   # node classification probe (csrc/label_probe.h)
+    SIGNATURES[f"clane_probe_forward_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p])
+    SIGNATURES[f"clane_probe_grad_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p])
+SIGNATURES["clane_probe_loss_ws_len"] = (_i64, [_i64, _i32])
+SIGNATURES["clane_probe_grad_ws_len"] = (_i64, [_i64, _i32, _i32])
+
+
+def probe_padded_classes(C_: int) -> int:
+    """Cp: the columns a fit takes in the stacked weights -- C rounded up to a power of two."""
+    if not 2 <= int(C_) <= PROBE_MAX_CLASSES:
+        raise ValueError(f"the label probe handles 2..{PROBE_MAX_CLASSES} classes, got {C_}")
+    return 1 << (int(C_) - 1).bit_length()
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
 _ACC = {torch.float32: torch.float32, torch.float64: torch.float64, torch.bfloat16: torch.float32}
@@ -404,6 +419,24 @@ class KernelBackend(abc.ABC):
         [B, n_slabs, 4] = (greater, equal_lower, equal_higher, eligible) among each slab's candidates; a pair without a
         rank: -1 / -inf."""
         raise NotImplementedError(f"{type(self).__name__} has no rank_count")
+
+    # node classification (classify.py): optional in the same way -- LabelProbe is the only caller.  rows are TABLE ROWS
+    # (int32), y int32 classes, split uint8 [n, >= F]; W [F * Cp, d], bias, G [n, F * Cp], dW, db in the accumulate dtype.
+    def probe_loss_ws_len(self, n: int, F: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no probe_loss_ws_len")
+
+    def probe_forward(self, Z, d: int, rows, y, split, W, bias, F: int, C: int, loss_ws, loss, G=None, pred=None):
+        """loss[f] = sum over the rows that train fit f (split[i, f] != 0) of the cross-entropy of softmax(Z[rows[i], :d] .
+        W_f^T + bias_f) against y[i] (float64 [F]); with ``G`` also G[i, f Cp + c] = split (p_c - [c == y_i]), with
+        ``pred`` (int32, [n, >= F]) the arg-max class of EVERY row, ties to the lowest class."""
+        raise NotImplementedError(f"{type(self).__name__} has no probe_forward")
+
+    def probe_grad_ws_len(self, n: int, K: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no probe_grad_ws_len")
+
+    def probe_grad(self, Z, d: int, rows, G, ws, dW, db):
+        """dW [K, d] = G^T . Z[rows, :d], db [K] = the column sums of G."""
+        raise NotImplementedError(f"{type(self).__name__} has no probe_grad")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -849,6 +882,51 @@ class HipKernels(KernelBackend):
                      None if excl_colidx is None else _vec(excl_colidx, torch.int32, "excl_colidx"),
                      int(bool(exclude_self)), n_slabs, _vec(target_score, acc, "target_score"),
                      _vec(counts, torch.int32, "counts"), self._stream(S))
+
+    # -- node classification probe -------------------------------------------------------
+    def probe_loss_ws_len(self, n: int, F: int) -> int:
+        return int(self.lib.clane_probe_loss_ws_len(n, F))
+
+    def probe_grad_ws_len(self, n: int, K: int, d: int) -> int:
+        return int(self.lib.clane_probe_grad_ws_len(n, K, d))
+
+    def probe_forward(self, Z, d: int, rows, y, split, W, bias, F: int, C: int, loss_ws, loss, G=None, pred=None):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        K = F * probe_padded_classes(C)
+        sp, lds = _mat(split, "split")
+        if split.dtype != torch.uint8 or split.shape[0] < n or split.shape[1] < F or y.numel() != n:
+            raise ValueError("probe_forward: split must be uint8 [n, >= F], y one class per row")
+        if tuple(W.shape) != (K, d) or bias.numel() != K:
+            raise ValueError(f"probe_forward: W must be [F * Cp, d] = [{K}, {d}] and bias [{K}], got {tuple(W.shape)}, "
+                             f"{tuple(bias.shape)}")
+        if loss.numel() < F or loss_ws.numel() < self.probe_loss_ws_len(n, F):
+            raise ValueError("probe_forward: loss needs F doubles, loss_ws probe_loss_ws_len(n, F)")
+        flags, gp, pp, ldp = 0, None, None, 0
+        if G is not None:
+            if G.numel() < n * K:
+                raise ValueError("probe_forward: G needs n * K elements")
+            flags, gp = flags | PROBE_WRITE_G, _vec(G, acc, "G")
+        if pred is not None:
+            pp, ldp = _mat(pred, "pred")
+            if pred.dtype != torch.int32 or pred.shape[0] < n or pred.shape[1] < F:
+                raise ValueError("probe_forward: pred must be int32 [n, >= F]")
+            flags |= PROBE_WRITE_PRED
+        self._invoke(self._fn("clane_probe_forward", Z.dtype), "clane_probe_forward",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), _vec(y, torch.int32, "y"), n, sp, lds,
+                     _vec(W, acc, "W"), _vec(bias, acc, "bias"), F, C, flags, gp, _vec(loss_ws, torch.float64, "loss_ws"),
+                     _vec(loss, torch.float64, "loss"), pp, ldp, self._stream(Z))
+
+    def probe_grad(self, Z, d: int, rows, G, ws, dW, db):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n, K = rows.numel(), db.numel()
+        if G.numel() < n * K or dW.numel() != K * d or ws.numel() < self.probe_grad_ws_len(n, K, d):
+            raise ValueError("probe_grad: G needs n * K elements, dW K * d, db K, ws probe_grad_ws_len(n, K, d)")
+        self._invoke(self._fn("clane_probe_grad", Z.dtype), "clane_probe_grad",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(G, acc, "G"), K,
+                     _vec(ws, acc, "ws"), _vec(dW, acc, "dW"), _vec(db, acc, "db"), self._stream(Z))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

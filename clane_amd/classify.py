@@ -1,0 +1,362 @@
+"""Node classification on a SweepEngine: the experiment the reference publishes (README.md:51-73) -- a multi-class
+logistic regression on the embeddings for train shares of 10 % ... 90 % and several random splits per share, micro and
+macro F1 -- with every fit of the table advancing at once on the card.
+
+The fits differ only in which rows train them.  Their weights are stacked (``W_all [F * Cp, d]``, ``Cp`` = the classes
+rounded up to a power of two), so one pass over the labelled rows is one dense contraction on the matrix cores with the
+soft-max, the loss, its gradient w.r.t. the logits and the arg-max fused in (csrc/label_probe.h), and the weights'
+gradient is the transposed contraction: ``Z`` is read once per pass instead of once per fit.  What remains for torch is
+a batched L-BFGS on the ``[F, Cp (d + 1)]`` parameters, the split masks and the integer confusion counts.
+
+Everything works on TABLE ROWS of the engine's tables (``eng.pos`` maps vertex -> table row).  One GPU only: a probe
+reads arbitrary rows of the table.
+
+Two things differ from ``tools/evaluate_f1.py`` on purpose: the splits are a seeded torch permutation, not scikit-learn's
+``train_test_split`` stream, and the optimiser is this module's L-BFGS, not scipy's -- the objective, its minimum and
+the F1 definitions are the same.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _hip
+from .train import require_one_gpu
+
+DEFAULT_RATIOS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
+G_BUDGET_BYTES = 8 << 30            # the [n, Fg * Cp] soft-max gradient of one group of fits
+
+
+# ---- labels, splits, metrics: host side -------------------------------------------------------------------------
+def read_labels(path: Path, vertex_ids: Sequence[str]) -> Tuple[List[int], List[int], List[str]]:
+    """(vertices, y, classes) of the ``id<TAB>class`` lines of ``path`` (empty lines skipped): any subset of the vertices
+    in any order; an id resolves as in the ``E`` file (first occurrence in ``V``).  An unknown or repeated id and a
+    malformed line are a ValueError naming the line.  Classes are indexed in sorted order."""
+    first = {}
+    for i, vid in enumerate(vertex_ids):
+        first.setdefault(str(vid), i)
+    vertices, names, seen = [], [], {}
+    with open(path, "r") as io:
+        for n, line in enumerate(io.read().split("\n")):
+            if not line.strip():
+                continue
+            parts = line.strip("\r").split("\t")
+            if len(parts) != 2:
+                raise ValueError(f"labels line {n + 1}: expected 'id\\tclass', got {line!r}")
+            vid, name = parts
+            if vid not in first:
+                raise ValueError(f"labels line {n + 1}: {vid!r} is not in list")
+            if vid in seen:
+                raise ValueError(f"labels line {n + 1}: {vid!r} was labelled on line {seen[vid]} already")
+            seen[vid] = n + 1
+            vertices.append(first[vid])
+            names.append(name)
+    classes = sorted(set(names))
+    index = {c: i for i, c in enumerate(classes)}
+    return vertices, [index[c] for c in names], classes
+
+
+def index_classes(labels: Sequence) -> Tuple[List[int], list]:
+    """(y, classes): arbitrary class names indexed in sorted order."""
+    classes = sorted(set(labels))
+    index = {c: i for i, c in enumerate(classes)}
+    return [index[c] for c in labels], classes
+
+
+def train_count(n: int, ratio: float) -> int:
+    """Rows that train at share ``ratio`` of ``n`` labelled rows: round(ratio n), half up, at least 1, at most n - 1."""
+    return min(n - 1, max(1, int(math.floor(ratio * n + 0.5))))
+
+
+def make_splits(n: int, ratios: Sequence[float], runs: int, seed: int) -> Tuple[torch.Tensor, List[Tuple[float, int]]]:
+    """(split uint8 [n, F] on the CPU, [(ratio, run)] per fit), F = len(ratios) * runs, ratio-major.  Run r permutes the n
+    labelled rows with a CPU generator seeded ``seed + r`` (the same permutation for every ratio, as a fixed
+    ``random_state`` gives in the tool); the first ``train_count`` rows of the permutation train, the rest test.  NOT
+    scikit-learn's split stream."""
+    if n < 2:
+        raise ValueError(f"a split needs at least 2 labelled vertices, got {n}")
+    if runs < 1 or not len(ratios) or any(not 0.0 < float(r) < 1.0 for r in ratios):
+        raise ValueError("ratios must lie in (0, 1) and runs be at least 1")
+    perms = [torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + r)) for r in range(runs)]
+    split = torch.zeros(n, len(ratios) * runs, dtype=torch.uint8)
+    fits = []
+    for a, ratio in enumerate(ratios):
+        for r in range(runs):
+            split[perms[r][:train_count(n, float(ratio))], a * runs + r] = 1
+            fits.append((float(ratio), r))
+    return split, fits
+
+
+def f1_from_confusion(conf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(micro, macro) F1 of confusion counts [..., C, C] (conf[t, p]: rows of true class t predicted p), as scikit-learn's
+    ``f1_score`` gives for single-label data: micro = accuracy; macro = the mean of the per-class F1 over the classes
+    that occur in the truth or in the predictions, a class without a true positive counting 0.  float64."""
+    conf = conf.double()
+    tp = torch.diagonal(conf, dim1=-2, dim2=-1)
+    truth, predicted = conf.sum(-1), conf.sum(-2)
+    denom = truth + predicted                               # 2 tp + fp + fn
+    f1 = torch.where(denom > 0, 2.0 * tp / denom.clamp(min=1.0), torch.zeros_like(denom))
+    present = (denom > 0).double()
+    macro = (f1 * present).sum(-1) / present.sum(-1).clamp(min=1.0)
+    micro = tp.sum(-1) / conf.sum((-2, -1)).clamp(min=1.0)
+    return micro, macro
+
+
+def confusion_counts(y: torch.Tensor, pred: torch.Tensor, test: torch.Tensor, C: int) -> torch.Tensor:
+    """int64 [F, C, C] from y [n], pred [n, F] and the test mask [n, F]: one integer bincount of y C + pred per fit."""
+    F = pred.shape[1]
+    key = (torch.arange(F, device=pred.device)[None, :] * C + y.long()[:, None]) * C + pred.long()
+    return torch.bincount(key[test], minlength=F * C * C).view(F, C, C)
+
+
+# ---- the fit ----------------------------------------------------------------------------------------------------
+@dataclass
+class ProbeFit:
+    W: torch.Tensor             # [F, C, d], accumulate dtype, on the device
+    b: torch.Tensor             # [F, C]
+    objective: torch.Tensor     # [F] float64: J_f at (W, b)
+    grad_max: torch.Tensor      # [F] float64: max |grad J_f| there
+    iterations: torch.Tensor    # [F] int64: accepted steps
+    converged: torch.Tensor     # [F] bool: grad_max <= gtol
+    skipped: torch.Tensor       # [F] bool: fewer than 2 classes among the training rows -- not fitted
+    pred: torch.Tensor          # [n, F] int32: arg-max class of EVERY row under fit f
+    n_train: torch.Tensor       # [F] int64
+
+
+class LabelProbe:
+    """F soft-max regressions on rows of a table of ``engine``, minimising per fit
+
+        J_f = (1 / n_f) [ sum_{i trains f} CE_i + (l2 / 2) ||W_f||^2 ],   bias unpenalised
+
+    (scikit-learn's ``LogisticRegression(C=1 / l2)`` up to the factor 1 / n_f) with a batched L-BFGS: memory ``memory``,
+    Armijo backtracking by halving, every fit with its own step, history and convergence flag; a fit is done when
+    ``max |grad J_f| <= gtol`` or after ``max_iter`` accepted steps, and done fits are frozen.  If the soft-max gradient
+    ``G [n, F Cp]`` would exceed ``g_budget_bytes`` the kernel passes run in groups of fits; the optimiser's state is one
+    tensor for all fits either way, and the kernels give a fit the same bits whatever shares its call, so the grouping
+    changes no result."""
+
+    C1 = 1e-4               # Armijo
+    MAX_HALVINGS = 40
+
+    def __init__(self, engine, l2: float = 1.0, gtol: float = 1e-4, max_iter: int = 2000, memory: int = 10,
+                 g_budget_bytes: int = G_BUDGET_BYTES):
+        try:
+            require_one_gpu(engine)
+        except NotImplementedError:
+            raise NotImplementedError(
+                f"the label probe runs on ONE GPU only: a fit reads arbitrary rows of the table, which this engine "
+                f"divides over {engine.world} ranks (exchange={engine.exchange!r}); several GPUs are out of scope") from None
+        if l2 < 0 or gtol <= 0 or max_iter < 0 or memory < 1 or g_budget_bytes < 1:
+            raise ValueError("LabelProbe: l2 >= 0, gtol > 0, max_iter >= 0, memory >= 1, g_budget_bytes >= 1")
+        self.eng, self.k = engine, engine.k
+        self.l2, self.gtol, self.max_iter, self.memory = float(l2), float(gtol), int(max_iter), int(memory)
+        self.g_budget_bytes = int(g_budget_bytes)
+        self.passes = {"forward": 0, "grad": 0}     # kernel calls of the last fit()
+
+    # ---- tables -------------------------------------------------------------------------------------------------
+    def table_and_rows(self, vertices, table: str = "Z"):
+        """(table, int32 rows) for vertex indices: the current embeddings ("Z") or the content embeddings ("X")."""
+        eng = self.eng
+        v = torch.as_tensor(vertices, dtype=torch.int64, device=eng.device).reshape(-1)
+        if v.numel() and (int(v.min()) < 0 or int(v.max()) >= eng.V):
+            raise ValueError(f"vertex indices must be in [0, {eng.V})")
+        if table == "Z":
+            return eng.Zcur, eng.pos[v].to(torch.int32).contiguous()
+        if table == "X":
+            xrow = getattr(eng, "_x_row_of_vertex", None)
+            if xrow is None:                      # X_loc is in local-row order: vertex -> local row, once per engine
+                verts = torch.from_numpy(eng.local.vertex).to(eng.device).long()
+                ok = verts >= 0
+                xrow = torch.full((eng.V,), -1, dtype=torch.int64, device=eng.device)
+                xrow[verts[ok]] = torch.arange(verts.numel(), device=eng.device)[ok]
+                eng._x_row_of_vertex = xrow
+            return eng.X_loc, xrow[v].to(torch.int32).contiguous()
+        raise ValueError(f"table must be 'Z' or 'X', got {table!r}")
+
+    def groups(self, n: int, F: int, Cp: int, acc: torch.dtype) -> List[Tuple[int, int]]:
+        per = max(1, self.g_budget_bytes // max(1, n * Cp * torch.empty(0, dtype=acc).element_size()))
+        return [(a, min(a + per, F)) for a in range(0, F, per)]
+
+    # ---- the batched fit ----------------------------------------------------------------------------------------
+    def fit(self, Z: torch.Tensor, rows: torch.Tensor, y: torch.Tensor, split: torch.Tensor, C: int) -> ProbeFit:
+        """Fit every column of ``split`` (uint8 [n, F]) on the rows ``rows`` (int32 table rows of ``Z``) with classes
+        ``y`` (integers in [0, C))."""
+        eng, k = self.eng, self.k
+        dev, d = Z.device, eng.d
+        acc = _hip.acc_dtype(Z.dtype)
+        Cp = _hip.probe_padded_classes(C)
+        n, F = int(rows.numel()), int(split.shape[1])
+        if split.dtype != torch.uint8 or split.dim() != 2 or split.shape[0] != n or y.numel() != n or F < 1:
+            raise ValueError("fit: split must be uint8 [n, F] and y hold one class per row")
+        rows = rows.to(dev, torch.int32).contiguous()
+        y = y.to(dev, torch.int32).contiguous()
+        if n and (int(y.min()) < 0 or int(y.max()) >= C):
+            raise ValueError(f"fit: classes must be in [0, {C})")
+        split = split.to(dev).contiguous()
+        groups = self.groups(n, F, Cp, acc)
+        Fg = max(b - a for a, b in groups)
+        G = torch.empty(n * Fg * Cp, dtype=acc, device=dev)
+        loss_ws = torch.empty(k.probe_loss_ws_len(n, Fg), dtype=torch.float64, device=dev)
+        grad_ws = torch.empty(k.probe_grad_ws_len(n, Fg * Cp, d), dtype=acc, device=dev)
+        dW = torch.empty(Fg * Cp * d, dtype=acc, device=dev)
+        db = torch.empty(Fg * Cp, dtype=acc, device=dev)
+        pred = torch.zeros(n, F, dtype=torch.int32, device=dev)
+        self.passes = {"forward": 0, "grad": 0}
+        nw, P = Cp * d, Cp * (d + 1)
+
+        trains = split != 0
+        n_train = trains.sum(0)
+        onehot = torch.zeros(n, C, dtype=torch.float64, device=dev)
+        onehot[torch.arange(n, device=dev), y.long()] = 1.0
+        classes_seen = ((trains.double().T @ onehot) > 0).sum(1)        # [F]: classes among a fit's training rows
+        skipped = classes_seen < 2
+        n_f = n_train.clamp(min=1).double()
+
+        def evaluate(x, want_grad, which=None, want_pred=False):
+            """(J [F], grad [F, P] or None) at x for the fits of the groups that hold a fit of the mask ``which``."""
+            loss = torch.zeros(F, dtype=torch.float64, device=dev)
+            g = torch.zeros(F, P, dtype=torch.float64, device=dev) if want_grad else None
+            need = None if which is None else which.tolist()
+            for a, b in groups:
+                if need is not None and not any(need[a:b]):
+                    continue
+                Wg = x[a:b, :nw].reshape((b - a) * Cp, d).to(acc).contiguous()
+                bg = x[a:b, nw:].reshape(-1).to(acc).contiguous()
+                k.probe_forward(Z, d, rows, y, split[:, a:b], Wg, bg, b - a, C, loss_ws, loss[a:b],
+                                G=G if want_grad else None, pred=pred[:, a:b] if want_pred else None)
+                self.passes["forward"] += 1
+                if want_grad:
+                    Kg = (b - a) * Cp
+                    k.probe_grad(Z, d, rows, G, grad_ws, dW[:Kg * d], db[:Kg])
+                    self.passes["grad"] += 1
+                    g[a:b, :nw] = dW[:Kg * d].view(b - a, nw).double()
+                    g[a:b, nw:] = db[:Kg].view(b - a, Cp).double()
+            Wm = x[:, :nw]
+            J = (loss + 0.5 * self.l2 * (Wm * Wm).sum(1)) / n_f
+            if want_grad:
+                g[:, :nw] += self.l2 * Wm
+                g /= n_f[:, None]
+            return J, g
+
+        eps = torch.finfo(acc).eps
+        x = torch.zeros(F, P, dtype=torch.float64, device=dev)
+        J, g = evaluate(x, True, ~skipped)
+        gmax = g.abs().amax(1)
+        done = skipped | (gmax <= self.gtol)
+        iterations = torch.zeros(F, dtype=torch.int64, device=dev)
+        m = self.memory
+        S = torch.zeros(m, F, P, dtype=torch.float64, device=dev)
+        Y = torch.zeros(m, F, P, dtype=torch.float64, device=dev)
+        rho = torch.zeros(m, F, dtype=torch.float64, device=dev)
+        gamma = torch.ones(F, dtype=torch.float64, device=dev)
+        has_hist = torch.zeros(F, dtype=torch.bool, device=dev)
+        head = count = 0
+
+        for _ in range(self.max_iter):
+            if bool(done.all()):
+                break
+            # the two-loop recursion, every fit with its own pairs (a slot a fit did not fill has rho = 0)
+            q = g.clone()
+            alphas = []
+            slots = [(head - 1 - j) % m for j in range(count)]          # newest first
+            for i in slots:
+                a_i = rho[i] * (S[i] * q).sum(1)
+                q -= a_i[:, None] * Y[i]
+                alphas.append(a_i)
+            r = q * gamma[:, None]
+            for i, a_i in zip(reversed(slots), reversed(alphas)):
+                b_i = rho[i] * (Y[i] * r).sum(1)
+                r += S[i] * (a_i - b_i)[:, None]
+            direction = -r
+            gd = (g * direction).sum(1)
+            uphill = ~(gd < 0)
+            direction = torch.where(uphill[:, None], -g, direction)
+            gd = torch.where(uphill, -(g * g).sum(1), gd)
+            t = torch.where(has_hist, torch.ones_like(gd), (1.0 / g.abs().sum(1).clamp(min=1e-300)).clamp(max=1.0))
+
+            searching = ~done
+            x_new, J_new, g_new = x.clone(), J.clone(), g.clone()
+            late = torch.zeros_like(done)
+            slack = 8.0 * eps * J.abs()
+            for trial in range(self.MAX_HALVINGS):
+                xt = torch.where(searching[:, None], x + t[:, None] * direction, x)
+                Jt, gt = evaluate(xt, trial == 0, searching)            # the first trial is usually taken: its gradient too
+                ok = searching & (Jt <= J + self.C1 * t * gd + slack)
+                x_new = torch.where(ok[:, None], xt, x_new)
+                J_new = torch.where(ok, Jt, J_new)
+                if trial == 0:
+                    g_new = torch.where(ok[:, None], gt, g_new)
+                else:
+                    late |= ok
+                searching = searching & ~ok
+                t = torch.where(searching, 0.5 * t, t)
+                if not bool(searching.any()):
+                    break
+            failed = searching
+            if bool(late.any()):
+                _, g2 = evaluate(x_new, True, late)
+                g_new = torch.where(late[:, None], g2, g_new)
+            moved = ~done & ~failed
+
+            s, yv = x_new - x, g_new - g
+            sy, yy = (s * yv).sum(1), (yv * yv).sum(1)
+            valid = moved & (sy > 1e-10 * yy) & (yy > 0)
+            S[head] = torch.where(valid[:, None], s, torch.zeros_like(s))
+            Y[head] = torch.where(valid[:, None], yv, torch.zeros_like(yv))
+            rho[head] = torch.where(valid, 1.0 / sy.clamp(min=1e-300), torch.zeros_like(sy))
+            gamma = torch.where(valid, sy / yy.clamp(min=1e-300), gamma)
+            head, count = (head + 1) % m, min(count + 1, m)
+            has_hist = has_hist | valid
+            # a fit whose search failed: once more from steepest descent, then it stops where it is
+            retry = failed & has_hist
+            rho[:, retry] = 0.0
+            gamma = torch.where(retry, torch.ones_like(gamma), gamma)
+            has_hist = has_hist & ~retry
+            x, J, g = x_new, J_new, g_new
+            iterations += moved.long()
+            gmax = g.abs().amax(1)
+            done = done | (gmax <= self.gtol) | (failed & ~retry) | (iterations >= self.max_iter)
+
+        evaluate(x, False, None, want_pred=True)
+        W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
+        b = x[:, nw:][:, :C].to(acc).contiguous()
+        return ProbeFit(W=W, b=b, objective=J, grad_max=gmax, iterations=iterations,
+                        converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train)
+
+    # ---- the experiment -----------------------------------------------------------------------------------------
+    def evaluate(self, vertices, y, n_classes: Optional[int] = None, ratios: Sequence[float] = DEFAULT_RATIOS,
+                 runs: int = 10, seed: int = 0, table: str = "Z") -> dict:
+        """The README's table for the labelled vertices (vertex indices, classes in [0, n_classes)): per ratio the mean
+        micro / macro F1 on the test rows over the runs whose training rows hold at least 2 classes."""
+        Z, rows = self.table_and_rows(vertices, table)
+        y = torch.as_tensor(y, dtype=torch.int64).reshape(-1)
+        C = int(n_classes) if n_classes is not None else int(y.max()) + 1
+        n = rows.numel()
+        if y.numel() != n:
+            raise ValueError("evaluate: one class per labelled vertex")
+        split, fits = make_splits(n, ratios, runs, seed)
+        fit = self.fit(Z, rows, y, split, C)
+        split_d = split.to(Z.device)
+        conf = confusion_counts(y.to(Z.device), fit.pred, split_d == 0, C)
+        micro, macro = f1_from_confusion(conf)
+        used = (~fit.skipped).double()
+        per_ratio = lambda v: (v * used).view(len(ratios), runs).sum(1)     # noqa: E731
+        n_used = per_ratio(torch.ones_like(used))
+        mean = lambda v: (per_ratio(v) / n_used.clamp(min=1.0)).tolist()    # noqa: E731
+        micro_r, macro_r, n_used = mean(micro), mean(macro), n_used.tolist()
+        nan = float("nan")
+        return {
+            "table": table, "labelled": n, "classes": C, "l2": self.l2, "seed": int(seed), "runs": int(runs),
+            "rows": [{"ratio": float(r), "micro_f1": micro_r[i] if n_used[i] else nan,
+                      "macro_f1": macro_r[i] if n_used[i] else nan, "runs_used": int(n_used[i])}
+                     for i, r in enumerate(ratios)],
+            "fits": {"ratio": [f[0] for f in fits], "run": [f[1] for f in fits],
+                     "iterations": fit.iterations.tolist(), "converged": fit.converged.tolist(),
+                     "objective": fit.objective.tolist(), "skipped": fit.skipped.tolist(),
+                     "micro_f1": micro.tolist(), "macro_f1": macro.tolist()},
+            "skipped_fits": int(fit.skipped.sum()),
+        }

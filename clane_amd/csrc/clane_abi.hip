@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "label_probe.h"
 #include "link_eval.h"
 #include "link_rank.h"
 #include "pair_train.h"
@@ -729,6 +730,64 @@ int pair_score(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_r
     return check_launch("pair_score");
 }
 
+// ---- node classification probe (label_probe.h) ----------------------------------------------------------------------
+inline int64_t probe_row_tiles(int64_t n) { return ceil_div(n > 0 ? n : 1, int64_t(kProjBM)); }
+inline int64_t probe_grad_chunks(int64_t n) { return ceil_div(n > 0 ? n : 1, int64_t(kGradChunk)); }
+
+template <typename T, typename A>
+int probe_forward(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, const int32_t *y, int64_t n,
+                  const uint8_t *split, int64_t ld_split, const A *W, const A *bias, int32_t F, int32_t C, int32_t flags,
+                  A *G, double *loss_ws, double *loss, int32_t *pred, int64_t ld_pred, void *stream) {
+    static_assert(kProbeWriteG == CLANE_PROBE_WRITE_G && kProbeWritePred == CLANE_PROBE_WRITE_PRED &&
+                      kProbeMaxClasses == CLANE_PROBE_MAX_CLASSES,
+                  "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d,
+            "probe_forward: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    REQUIRE(C >= 2 && C <= kProbeMaxClasses, "probe_forward: C must be in [2, %d], got %d", kProbeMaxClasses, C);
+    const int cp_log = probe_cp_log(C);
+    REQUIRE(F >= 1 && F <= (INT32_MAX >> 7), "probe_forward: bad number of fits %d", F);
+    REQUIRE(ld_split >= F, "probe_forward: ld_split %lld < F = %d", (long long)ld_split, F);
+    REQUIRE((flags & ~(CLANE_PROBE_WRITE_G | CLANE_PROBE_WRITE_PRED)) == 0, "probe_forward: unknown flags %d", flags);
+    REQUIRE(!(flags & CLANE_PROBE_WRITE_PRED) || ld_pred >= F, "probe_forward: ld_pred %lld < F = %d", (long long)ld_pred, F);
+    REQUIRE(loss_ws && loss, "probe_forward: null loss workspace/output");
+    REQUIRE(n == 0 || (Z && rows && y && split && W && bias), "probe_forward: null pointer");
+    REQUIRE(n == 0 || !(flags & CLANE_PROBE_WRITE_G) || G, "probe_forward: CLANE_PROBE_WRITE_G needs G");
+    REQUIRE(n == 0 || !(flags & CLANE_PROBE_WRITE_PRED) || pred, "probe_forward: CLANE_PROBE_WRITE_PRED needs pred");
+    const int K = F << cp_log;
+    const int n_tiles = int(ceil_div(int64_t(K), int64_t(kProjBN)));
+    const int64_t row_tiles = n > 0 ? probe_row_tiles(n) : 0;
+    const int64_t blocks = row_tiles * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "probe_forward: %lld rows x %d fits is too many for one launch", (long long)n, F);
+    if (blocks > 0)
+        probe_forward_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, y, n, split, ld_split, W, bias, F, C, cp_log, flags, G, loss_ws, pred, ld_pred,
+            n_tiles);
+    probe_loss_reduce_kernel<<<unsigned(F), kBlock, 0, (hipStream_t)stream>>>(loss_ws, row_tiles, F, loss);
+    return check_launch("probe_forward");
+}
+
+template <typename T, typename A>
+int probe_grad(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *G,
+               int32_t K, A *ws, A *dW, A *db, void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d && K >= 1,
+            "probe_grad: bad shape rows=%lld n=%lld d=%d ldz=%lld K=%d", (long long)table_rows, (long long)n, d,
+            (long long)ldz, K);
+    REQUIRE(ws && dW && db, "probe_grad: null workspace/output");
+    REQUIRE(n == 0 || (Z && rows && G), "probe_grad: null pointer");
+    const int64_t n_chunks = n > 0 ? probe_grad_chunks(n) : 0;
+    REQUIRE(n_chunks <= 65535, "probe_grad: %lld rows is too many for one launch", (long long)n);
+    const int64_t d_tiles = ceil_div(int64_t(d), int64_t(kProjBN)), k_tiles = ceil_div(int64_t(K), int64_t(kProjBM));
+    REQUIRE(d_tiles * k_tiles <= INT32_MAX, "probe_grad: K=%d x d=%d is too many tiles for one launch", K, d);
+    const int64_t len = int64_t(K) * (int64_t(d) + 1);
+    if (n_chunks > 0)
+        probe_grad_kernel<T, A><<<dim3(unsigned(d_tiles * k_tiles), unsigned(n_chunks)), kBlock, 0, (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, n, G, K, ws, int(d_tiles));
+    probe_grad_reduce_kernel<A><<<unsigned(ceil_div(len, kBlock)), kBlock, 0, (hipStream_t)stream>>>(
+        ws, n_chunks, len, int64_t(K) * d, dW, db);
+    return check_launch("probe_grad");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1093,6 +1152,28 @@ int clane_rank_merge_f32(const float *cand_score, const int32_t *cand_id, int64_
 int clane_rank_merge_f64(const double *cand_score, const int32_t *cand_id, int64_t Q, int32_t n_slabs, int32_t k,
                          double *out_score, int32_t *out_id, void *stream) {
     return rank_merge<double>(cand_score, cand_id, Q, n_slabs, k, out_score, out_id, stream);
+}
+
+#define CLANE_PROBE_WRAPPERS(SUF, CT, T, AT)                                                                           \
+    int clane_probe_forward_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \
+                                  const int32_t *y, int64_t n, const uint8_t *split, int64_t ld_split, const AT *W,    \
+                                  const AT *bias, int32_t F, int32_t C, int32_t flags, AT *G, double *loss_ws,         \
+                                  double *loss, int32_t *pred, int64_t ld_pred, void *stream) {                        \
+        return probe_forward<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, y, n, split, ld_split,   \
+                                    W, bias, F, C, flags, G, loss_ws, loss, pred, ld_pred, stream);                    \
+    }                                                                                                                  \
+    int clane_probe_grad_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,           \
+                               int64_t n, const AT *G, int32_t K, AT *ws, AT *dW, AT *db, void *stream) {              \
+        return probe_grad<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, G, K, ws, dW, db,        \
+                                 stream);                                                                              \
+    }
+CLANE_PROBE_WRAPPERS(f32, float, float, float)
+CLANE_PROBE_WRAPPERS(f64, double, double, double)
+CLANE_PROBE_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_PROBE_WRAPPERS
+int64_t clane_probe_loss_ws_len(int64_t n, int32_t F) { return probe_row_tiles(n) * (F > 0 ? F : 0); }
+int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d) {
+    return probe_grad_chunks(n) * (K > 0 ? K : 0) * (int64_t(d > 0 ? d : 0) + 1);
 }
 
 }  // extern "C"

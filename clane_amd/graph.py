@@ -509,6 +509,34 @@ class Graph(torch.utils.data.Dataset):
                 f"kernel to score all pairs with")
         return LinkRanker(eng, similarity).evaluate(src, dst, hits, filter_existing).as_dict()
 
+    def evaluate_labels(self, labels, ratios=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), runs: int = 10, seed: int = 0,
+                        l2: float = 1.0, table: str = "Z") -> dict:
+        """The reference README's node-classification table for the CURRENT embeddings (extension): a soft-max regression
+        on the labelled vertices' rows per (train share, random split), all fits at once on the GPU (classify.py), micro
+        and macro F1 on each fit's test rows, averaged over the runs of a share.  ``labels``: a file of ``id<TAB>class``
+        lines (any subset of the vertices), a pair ``(vertex indices, classes)``, or one class per vertex; class names
+        are indexed in sorted order.  ``table="X"`` probes the content embeddings instead (the README's bag-of-words
+        row).  Returns ``{"table", "labelled", "classes", "class_names", "rows": [{"ratio", "micro_f1", "macro_f1",
+        "runs_used"}], "fits": {...per fit: ratio, run, iterations, converged, objective, skipped, micro_f1, macro_f1},
+        ...}``.  Several GPUs and a column division raise NotImplementedError."""
+        from .classify import LabelProbe, index_classes, read_labels
+        if isinstance(labels, (str, Path)):
+            vertices, y, names = read_labels(Path(labels), self.vertex_ids)
+        else:
+            if isinstance(labels, tuple) and len(labels) == 2:
+                vertices, raw = list(labels[0]), list(labels[1])
+            else:
+                raw = list(labels)
+                vertices = list(range(len(self)))
+            if len(raw) != len(vertices):
+                raise ValueError("evaluate_labels: one class per labelled vertex")
+            raw = [c.item() if isinstance(c, torch.Tensor) else c for c in raw]
+            y, names = index_classes(raw)
+        out = LabelProbe(self.engine(), l2=l2).evaluate(vertices, y, len(names), ratios=tuple(ratios), runs=runs,
+                                                        seed=seed, table=table)
+        out["class_names"] = [str(c) for c in names]
+        return out
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

@@ -52,7 +52,10 @@ extern "C" {
                              *    + clane_rank_scores_*, clane_rank_merge_*, clane_pair_score_* (link prediction: top-k
                              *    candidates of query rows against the whole table, scores of explicit pairs)
                              *    + clane_rank_count_* (held-out link evaluation: a pair's score and how many eligible rows of
-                             *    the whole table score above it or tie with it -- the filtered rank without a score matrix) */
+                             *    the whole table score above it or tie with it -- the filtered rank without a score matrix)
+                             *    + clane_probe_forward_*, clane_probe_grad_*, clane_probe_loss_ws_len,
+                             *    clane_probe_grad_ws_len (node classification: F stacked soft-max regressions on rows of the
+                             *    table, loss / gradient / arg-max fused into the logits' contraction) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -546,6 +549,42 @@ int clane_rank_count_bf16(const uint16_t *S, int64_t lds, const uint16_t *N, int
                          const float *sq, const int32_t *label, const int64_t *excl_rowptr,
                          const int32_t *excl_colidx, int32_t exclude_self, int32_t n_slabs, float *target_score,
                          int32_t *counts, void *stream);
+
+/* ---- node classification probe (csrc/label_probe.h) ------------------------------------------------------------------
+ * F multi-class logistic regressions on the rows `rows[0..n)` of the table Z (an index outside [0, table_rows) reads as a
+ * zero row), classes y[i] in [0, C), 2 <= C <= CLANE_PROBE_MAX_CLASSES.  The fits' weights are stacked: W [K, d] and
+ * bias [K] in the accumulate type, K = F * Cp, fit f's class c in row f * Cp + c, Cp = C rounded up to a power of two
+ * (rows of pad classes are ignored).  split [n, ld_split >= F] (uint8): row i trains fit f where split[i, f] != 0.
+ *
+ * forward: logits = Z[rows] . W^T + bias never reach memory; per (row, fit) the log-sum-exp over the C real classes gives
+ *   loss[f] = sum_i split[i, f] (lse - logit[y_i])                (always; double; loss_ws: probe_loss_ws_len doubles)
+ *   G[i, f Cp + c] = split[i, f] (p_c - [c == y_i]), pad columns 0   (CLANE_PROBE_WRITE_G; G is [n, K] contiguous)
+ *   pred[i, f] = argmax_c, ties to the lowest class, every row      (CLANE_PROBE_WRITE_PRED; pred is [n, ld_pred >= F])
+ * grad: dW [K, d] = G^T . Z[rows], db [K] = sum_i G[i, :] (ws: probe_grad_ws_len elements of the accumulate type).
+ * No atomics: two calls give the same bits, and a fit's results do not depend on the other fits of the call. */
+#define CLANE_PROBE_MAX_CLASSES 64
+#define CLANE_PROBE_WRITE_G 1
+#define CLANE_PROBE_WRITE_PRED 2
+int clane_probe_forward_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                            const int32_t *y, int64_t n, const uint8_t *split, int64_t ld_split, const float *W,
+                            const float *bias, int32_t F, int32_t C, int32_t flags, float *G, double *loss_ws,
+                            double *loss, int32_t *pred, int64_t ld_pred, void *stream);
+int clane_probe_forward_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                            const int32_t *y, int64_t n, const uint8_t *split, int64_t ld_split, const double *W,
+                            const double *bias, int32_t F, int32_t C, int32_t flags, double *G, double *loss_ws,
+                            double *loss, int32_t *pred, int64_t ld_pred, void *stream);
+int clane_probe_forward_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                             const int32_t *y, int64_t n, const uint8_t *split, int64_t ld_split, const float *W,
+                             const float *bias, int32_t F, int32_t C, int32_t flags, float *G, double *loss_ws,
+                             double *loss, int32_t *pred, int64_t ld_pred, void *stream);
+int clane_probe_grad_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                         const float *G, int32_t K, float *ws, float *dW, float *db, void *stream);
+int clane_probe_grad_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                         const double *G, int32_t K, double *ws, double *dW, double *db, void *stream);
+int clane_probe_grad_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          const float *G, int32_t K, float *ws, float *dW, float *db, void *stream);
+int64_t clane_probe_loss_ws_len(int64_t n, int32_t F);
+int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,9 @@ multi-class logistic regression on Z, train ratio 10 %...90 %, several random sp
 
 `Y` holds one `id<TAB>class` per line in the order of `V` (the reference ships such a file for the karate
 graph, tests/data_root/Y, but no code reads it).  Not on the hot path; needs scikit-learn.
+
+The same experiment on the GPU, from the engine's tables and without scikit-learn: the `node_classification` section of
+a config / `Graph.evaluate_labels` (clane_amd/classify.py).
 """
 import argparse
 from pathlib import Path

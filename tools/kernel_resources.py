@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Registers / occupancy / LDS of every kernel in libclane_hip.so, from hipcc's -Rpass-analysis=kernel-resource-usage
-(cross-compiles without a GPU).  Usage: python tools/kernel_resources.py [substring ...]"""
+(cross-compiles without a GPU).  Usage: python tools/kernel_resources.py [substring ...]
+e.g. `python tools/kernel_resources.py probe_` for the label probe's kernels (DESIGN.md section 6.10's table)."""
 import re
 import subprocess
 import sys
