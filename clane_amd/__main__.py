@@ -67,6 +67,15 @@ def embedding(args):
             raise NotImplementedError("node_classification runs on one GPU only; several GPUs are out of scope")
         if not isinstance(node_cls, dict) or "labels" not in node_cls:
             raise ValueError("node_classification: the section needs 'labels', the file of id<TAB>class lines")
+    # optional section (extension): node_clustering: {labels: Y, clusters: 7, restarts: 10, seed: 0, max_iter: 300,
+    # baseline: true, assignments: true}
+    node_clu = hparams.get("node_clustering") if isinstance(hparams, dict) else None
+    if node_clu is not None:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                    # before any work, as node_classification
+            raise NotImplementedError("node_clustering runs on one GPU only; several GPUs are out of scope")
+        if not isinstance(node_clu, dict) or ("labels" not in node_clu and "clusters" not in node_clu):
+            raise ValueError("node_clustering: the section needs 'labels', the file of id<TAB>class lines, or 'clusters', "
+                             "the number of clusters")
 
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
@@ -184,6 +193,35 @@ def embedding(args):
                                   for name, t in tables.items()}}, io, indent=1)
             io.write("\n")
         say(f"The F1 table of {first['labelled']} labelled vertices is stored in {out.absolute()}.")
+
+    if node_clu is not None:                        # k-means on the embeddings the run ends with
+        import json
+        labels_file = None
+        if "labels" in node_clu:
+            labels_file = Path(node_clu["labels"])
+            if not labels_file.is_absolute():
+                labels_file = Path(args.data_root) / labels_file
+        kw = {key: node_clu[key] for key in ("restarts", "seed", "max_iter") if key in node_clu}
+        kw.update(k=node_clu.get("clusters"), labels=labels_file, return_assignments=True)
+        tables = {"Z": g.cluster(table="Z", **kw)}
+        if node_clu.get("baseline", False):
+            tables["X"] = g.cluster(table="X", **kw)
+        first = tables["Z"]
+        hidden = ("vertices", "assignments", "class_names", "table", "clustered", "clusters", "restarts", "seed")
+        out = args.output_root.joinpath('cluster_metrics.json')
+        with open(out, "w") as io:
+            json.dump({"labels": None if labels_file is None else str(labels_file), "clustered": first["clustered"],
+                       "class_names": first.get("class_names"), "clusters": first["clusters"],
+                       "restarts": first["restarts"], "seed": first["seed"],
+                       "tables": {name: {key: v for key, v in t.items() if key not in hidden}
+                                  for name, t in tables.items()}}, io, indent=1)
+            io.write("\n")
+        if node_clu.get("assignments", False):
+            with open(args.output_root.joinpath('clusters.tsv'), "w") as io:
+                for v, c in zip(first["vertices"], first["assignments"]):
+                    io.write(f"{g.vertex_ids[v]}\t{c}\n")
+        say(f"The clustering of {first['clustered']} vertices into {first['clusters']} clusters is stored in "
+            f"{out.absolute()}.")
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

@@ -105,6 +105,12 @@ for _s in ("f32", "f64", "bf16"):   # node classification probe (csrc/label_prob
     SIGNATURES[f"clane_probe_grad_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p])
 SIGNATURES["clane_probe_loss_ws_len"] = (_i64, [_i64, _i32])
 SIGNATURES["clane_probe_grad_ws_len"] = (_i64, [_i64, _i32, _i32])
+for _s in ("f32", "f64", "bf16"):   # node clustering (csrc/kmeans.h)
+    SIGNATURES[f"clane_kmeans_assign_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p])
+    SIGNATURES[f"clane_kmeans_update_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p])
+SIGNATURES["clane_kmeans_update_ws_len"] = (_i64, [_i64, _i32, _i32, _i32])
 
 
 def probe_padded_classes(C_: int) -> int:
@@ -437,6 +443,21 @@ class KernelBackend(abc.ABC):
     def probe_grad(self, Z, d: int, rows, G, ws, dW, db):
         """dW [K, d] = G^T . Z[rows, :d], db [K] = the column sums of G."""
         raise NotImplementedError(f"{type(self).__name__} has no probe_grad")
+
+    # node clustering (cluster.py): optional in the same way -- KMeans is the only caller.  rows / order are TABLE ROWS
+    # (int32); centres [R, K, d], csq [R, K], best and the workspace in the accumulate dtype.
+    def kmeans_assign(self, Z, d: int, rows, centres, csq, assign, best):
+        """assign[i, r] (int32, [n, >= R]) = the centre of restart r nearest to Z[rows[i], :d], ties to the lowest index;
+        best[i, r] = min_j (csq[r, j] - 2 z_i . c[r, j]): the squared distance without |z_i|^2."""
+        raise NotImplementedError(f"{type(self).__name__} has no kmeans_assign")
+
+    def kmeans_update_ws_len(self, n: int, R: int, K: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no kmeans_update_ws_len")
+
+    def kmeans_update(self, Z, d: int, order, seg, centres_old, ws, centres_new, csq_new):
+        """centres_new[r, j] = the mean of the table rows order[seg[r K + j] : seg[r K + j + 1]] (the old centre where
+        the segment is empty), csq_new its squared norm.  order holds restart r's n rows at [r n, (r + 1) n)."""
+        raise NotImplementedError(f"{type(self).__name__} has no kmeans_update")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -927,6 +948,44 @@ class HipKernels(KernelBackend):
         self._invoke(self._fn("clane_probe_grad", Z.dtype), "clane_probe_grad",
                      zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(G, acc, "G"), K,
                      _vec(ws, acc, "ws"), _vec(dW, acc, "dW"), _vec(db, acc, "db"), self._stream(Z))
+
+    # -- node clustering -------------------------------------------------------------------
+    def kmeans_update_ws_len(self, n: int, R: int, K: int, d: int) -> int:
+        return int(self.lib.clane_kmeans_update_ws_len(n, R, K, d))
+
+    def kmeans_assign(self, Z, d: int, rows, centres, csq, assign, best):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        if centres.dim() != 3 or centres.shape[2] != d or tuple(csq.shape) != tuple(centres.shape[:2]):
+            raise ValueError(f"kmeans_assign: centres must be [R, K, d = {d}] and csq [R, K], got {tuple(centres.shape)}, "
+                             f"{tuple(csq.shape)}")
+        R, K = int(centres.shape[0]), int(centres.shape[1])
+        ap, lda = _mat(assign, "assign")
+        bp, ldb = _mat(best, "best")
+        if assign.dtype != torch.int32 or best.dtype != acc or min(assign.shape[0], best.shape[0]) < n \
+                or min(assign.shape[1], best.shape[1]) < R:
+            raise ValueError(f"kmeans_assign: assign must be int32 [n, >= R] and best {acc} [n, >= R]")
+        self._invoke(self._fn("clane_kmeans_assign", Z.dtype), "clane_kmeans_assign",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(centres, acc, "centres"),
+                     _vec(csq, acc, "csq"), R, K, ap, lda, bp, ldb, self._stream(Z))
+
+    def kmeans_update(self, Z, d: int, order, seg, centres_old, ws, centres_new, csq_new):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        if centres_old.dim() != 3 or centres_old.shape[2] != d or centres_new.shape != centres_old.shape \
+                or tuple(csq_new.shape) != tuple(centres_old.shape[:2]):
+            raise ValueError(f"kmeans_update: centres_old / centres_new must be [R, K, d = {d}] and csq_new [R, K]")
+        R, K = int(centres_old.shape[0]), int(centres_old.shape[1])
+        if order.numel() % R or seg.numel() != R * K + 1:
+            raise ValueError("kmeans_update: order needs R * n rows and seg R * K + 1 offsets")
+        n = order.numel() // R
+        if ws.numel() < self.kmeans_update_ws_len(n, R, K, d):
+            raise ValueError("kmeans_update: ws needs kmeans_update_ws_len(n, R, K, d) elements")
+        self._invoke(self._fn("clane_kmeans_update", Z.dtype), "clane_kmeans_update",
+                     zp, Z.shape[0], d, ldz, _vec(order, torch.int32, "order"), _vec(seg, torch.int64, "seg"), n, R, K,
+                     _vec(centres_old, acc, "centres_old"), _vec(ws, acc, "ws"), _vec(centres_new, acc, "centres_new"),
+                     _vec(csq_new, acc, "csq_new"), self._stream(Z))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

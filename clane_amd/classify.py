@@ -113,6 +113,26 @@ def confusion_counts(y: torch.Tensor, pred: torch.Tensor, test: torch.Tensor, C:
     return torch.bincount(key[test], minlength=F * C * C).view(F, C, C)
 
 
+# ---- tables (shared with cluster.KMeans) --------------------------------------------------------------------------
+def table_and_rows(eng, vertices, table: str = "Z"):
+    """(table, int32 rows) for vertex indices: the current embeddings ("Z") or the content embeddings ("X")."""
+    v = torch.as_tensor(vertices, dtype=torch.int64, device=eng.device).reshape(-1)
+    if v.numel() and (int(v.min()) < 0 or int(v.max()) >= eng.V):
+        raise ValueError(f"vertex indices must be in [0, {eng.V})")
+    if table == "Z":
+        return eng.Zcur, eng.pos[v].to(torch.int32).contiguous()
+    if table == "X":
+        xrow = getattr(eng, "_x_row_of_vertex", None)
+        if xrow is None:                      # X_loc is in local-row order: vertex -> local row, once per engine
+            verts = torch.from_numpy(eng.local.vertex).to(eng.device).long()
+            ok = verts >= 0
+            xrow = torch.full((eng.V,), -1, dtype=torch.int64, device=eng.device)
+            xrow[verts[ok]] = torch.arange(verts.numel(), device=eng.device)[ok]
+            eng._x_row_of_vertex = xrow
+        return eng.X_loc, xrow[v].to(torch.int32).contiguous()
+    raise ValueError(f"table must be 'Z' or 'X', got {table!r}")
+
+
 # ---- the fit ----------------------------------------------------------------------------------------------------
 @dataclass
 class ProbeFit:
@@ -160,22 +180,7 @@ class LabelProbe:
     # ---- tables -------------------------------------------------------------------------------------------------
     def table_and_rows(self, vertices, table: str = "Z"):
         """(table, int32 rows) for vertex indices: the current embeddings ("Z") or the content embeddings ("X")."""
-        eng = self.eng
-        v = torch.as_tensor(vertices, dtype=torch.int64, device=eng.device).reshape(-1)
-        if v.numel() and (int(v.min()) < 0 or int(v.max()) >= eng.V):
-            raise ValueError(f"vertex indices must be in [0, {eng.V})")
-        if table == "Z":
-            return eng.Zcur, eng.pos[v].to(torch.int32).contiguous()
-        if table == "X":
-            xrow = getattr(eng, "_x_row_of_vertex", None)
-            if xrow is None:                      # X_loc is in local-row order: vertex -> local row, once per engine
-                verts = torch.from_numpy(eng.local.vertex).to(eng.device).long()
-                ok = verts >= 0
-                xrow = torch.full((eng.V,), -1, dtype=torch.int64, device=eng.device)
-                xrow[verts[ok]] = torch.arange(verts.numel(), device=eng.device)[ok]
-                eng._x_row_of_vertex = xrow
-            return eng.X_loc, xrow[v].to(torch.int32).contiguous()
-        raise ValueError(f"table must be 'Z' or 'X', got {table!r}")
+        return table_and_rows(self.eng, vertices, table)
 
     def groups(self, n: int, F: int, Cp: int, acc: torch.dtype) -> List[Tuple[int, int]]:
         per = max(1, self.g_budget_bytes // max(1, n * Cp * torch.empty(0, dtype=acc).element_size()))

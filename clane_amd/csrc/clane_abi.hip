@@ -12,6 +12,7 @@
 #include "build_p.h"
 #include "edge_score.h"
 #include "device_utils.h"
+#include "kmeans.h"
 #include "label_probe.h"
 #include "link_eval.h"
 #include "link_rank.h"
@@ -788,6 +789,58 @@ int probe_grad(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int
     return check_launch("probe_grad");
 }
 
+// ---- node clustering (kmeans.h) ---------------------------------------------------------------------------------------
+inline int64_t kmeans_windows(int64_t n, int64_t R) { return ceil_div(n > 0 && R > 0 ? n * R : 1, int64_t(kKmChunk)); }
+
+template <typename T, typename A>
+int kmeans_assign(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *centres,
+                  const A *csq, int32_t R, int32_t K, int32_t *assign, int64_t ld_assign, A *best, int64_t ld_best,
+                  void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d >= 1 && ldz >= d, "kmeans_assign: bad shape rows=%lld n=%lld d=%d ldz=%lld",
+            (long long)table_rows, (long long)n, d, (long long)ldz);
+    REQUIRE(K >= 1, "kmeans_assign: K must be at least 1, got %d", K);
+    REQUIRE(R >= 1 && R <= 65535, "kmeans_assign: R must be in [1, 65535], got %d", R);
+    REQUIRE(ld_assign >= R, "kmeans_assign: ld_assign %lld < R = %d", (long long)ld_assign, R);
+    REQUIRE(ld_best >= R, "kmeans_assign: ld_best %lld < R = %d", (long long)ld_best, R);
+    REQUIRE(assign && best, "kmeans_assign: null output");
+    REQUIRE(n == 0 || (Z && rows && centres && csq), "kmeans_assign: null pointer");
+    if (n == 0) return CLANE_OK;
+    const int64_t row_tiles = ceil_div(n, int64_t(kProjBM));
+    REQUIRE(row_tiles <= INT32_MAX, "kmeans_assign: %lld rows is too many for one launch", (long long)n);
+    kmeans_assign_kernel<T, A><<<dim3(unsigned(row_tiles), unsigned(R)), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, rows, n, centres, csq, K, assign, ld_assign, best, ld_best);
+    return check_launch("kmeans_assign");
+}
+
+template <typename T, typename A>
+int kmeans_update(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, const int64_t *seg,
+                  int64_t n, int32_t R, int32_t K, const A *centres_old, A *ws, A *centres_new, A *csq_new, void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d >= 1 && ldz >= d, "kmeans_update: bad shape rows=%lld n=%lld d=%d ldz=%lld",
+            (long long)table_rows, (long long)n, d, (long long)ldz);
+    REQUIRE(K >= 1, "kmeans_update: K must be at least 1, got %d", K);
+    REQUIRE(R >= 1, "kmeans_update: R must be at least 1, got %d", R);
+    REQUIRE(int64_t(R) * K <= INT32_MAX, "kmeans_update: R=%d x K=%d is too many centres for one launch", R, K);
+    REQUIRE(n <= INT64_MAX / R && kmeans_windows(n, R) <= INT32_MAX, "kmeans_update: %lld rows x %d restarts is too many "
+            "for one launch", (long long)n, R);
+    REQUIRE(ws && centres_new && csq_new, "kmeans_update: null workspace/output");
+    REQUIRE(seg && centres_old, "kmeans_update: null pointer");
+    REQUIRE(n == 0 || (Z && order), "kmeans_update: null pointer");
+    const int64_t total = n * R, n_seg = int64_t(R) * K;
+    if (total > 0) {
+        const int lpr_log = km_lpr_log<T>(d);
+        const unsigned grid = unsigned(kmeans_windows(n, R));
+        if (aligned16(Z) && ldz % Elem<T>::kVec == 0 && d % Elem<T>::kVec == 0)
+            kmeans_chunk_kernel<T, A, true><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                Z, table_rows, d, ldz, order, total, seg, n_seg, lpr_log, centres_new, ws);
+        else
+            kmeans_chunk_kernel<T, A, false><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                Z, table_rows, d, ldz, order, total, seg, n_seg, lpr_log, centres_new, ws);
+    }
+    kmeans_finish_kernel<A><<<unsigned(n_seg), kBlock, 0, (hipStream_t)stream>>>(seg, total, d, centres_old, ws,
+                                                                                centres_new, csq_new);
+    return check_launch("kmeans_update");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1174,6 +1227,28 @@ CLANE_PROBE_WRAPPERS(bf16, uint16_t, bf16_t, float)
 int64_t clane_probe_loss_ws_len(int64_t n, int32_t F) { return probe_row_tiles(n) * (F > 0 ? F : 0); }
 int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d) {
     return probe_grad_chunks(n) * (K > 0 ? K : 0) * (int64_t(d > 0 ? d : 0) + 1);
+}
+
+#define CLANE_KMEANS_WRAPPERS(SUF, CT, T, AT)                                                                          \
+    int clane_kmeans_assign_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \
+                                  int64_t n, const AT *centres, const AT *csq, int32_t R, int32_t K, int32_t *assign,  \
+                                  int64_t ld_assign, AT *best, int64_t ld_best, void *stream) {                        \
+        return kmeans_assign<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, centres, csq, R, K,   \
+                                    assign, ld_assign, best, ld_best, stream);                                         \
+    }                                                                                                                  \
+    int clane_kmeans_update_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,       \
+                                  const int64_t *seg, int64_t n, int32_t R, int32_t K, const AT *centres_old, AT *ws,  \
+                                  AT *centres_new, AT *csq_new, void *stream) {                                        \
+        return kmeans_update<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, order, seg, n, R, K,           \
+                                    centres_old, ws, centres_new, csq_new, stream);                                    \
+    }
+CLANE_KMEANS_WRAPPERS(f32, float, float, float)
+CLANE_KMEANS_WRAPPERS(f64, double, double, double)
+CLANE_KMEANS_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_KMEANS_WRAPPERS
+int64_t clane_kmeans_update_ws_len(int64_t n, int32_t R, int32_t K, int32_t d) {
+    (void)K;                                     /* two chunk sums per window of the sorted list, whatever K */
+    return 2 * kmeans_windows(n, R) * int64_t(d > 0 ? d : 0);
 }
 
 }  // extern "C"

@@ -537,6 +537,46 @@ class Graph(torch.utils.data.Dataset):
         out["class_names"] = [str(c) for c in names]
         return out
 
+    def cluster(self, k=None, labels=None, vertices=None, restarts: int = 10, seed: int = 0, max_iter: int = 300,
+                table: str = "Z", return_assignments: bool = False) -> dict:
+        """Node clustering of the CURRENT embeddings (extension): k-means, every restart at once on the GPU
+        (cluster.py), the restart of lowest inertia reported.  With ``labels`` -- the three forms ``evaluate_labels``
+        takes -- the labelled vertices are clustered, ``k`` defaults to the number of classes and the result carries
+        ``nmi``, ``ari``, ``purity``, ``per_restart`` and ``class_names``; without, ``vertices`` (default: all) are
+        clustered into ``k`` clusters.  ``table="X"`` clusters the content embeddings instead.  Returns ``{"table",
+        "clustered", "clusters", "restarts", "seed", "inertia", "iterations", "converged", "empty", "best_restart",
+        "sizes", ...}``; with ``return_assignments`` also ``"vertices"`` and ``"assignments"`` (the best restart's
+        cluster per clustered vertex).  Several GPUs and a column division raise NotImplementedError."""
+        from .classify import index_classes, read_labels
+        if k is None and labels is None:
+            raise ValueError("cluster: give k, the number of clusters, or labels whose classes it defaults to")
+        y = names = None
+        if labels is not None:
+            if isinstance(labels, (str, Path)):
+                vertices, y, names = read_labels(Path(labels), self.vertex_ids)
+            else:
+                if isinstance(labels, tuple) and len(labels) == 2:
+                    vertices, raw = list(labels[0]), list(labels[1])
+                else:
+                    raw = list(labels)
+                    vertices = list(range(len(self)))
+                if len(raw) != len(vertices):
+                    raise ValueError("cluster: one class per labelled vertex")
+                raw = [c.item() if isinstance(c, torch.Tensor) else c for c in raw]
+                y, names = index_classes(raw)
+        elif vertices is None:
+            vertices = list(range(len(self)))
+        from .cluster import KMeans
+        km = KMeans(self.engine(), max_iter=max_iter)
+        out = km.evaluate(vertices, k=k, y=y, n_classes=None if names is None else len(names), restarts=restarts,
+                          seed=seed, table=table)
+        if names is not None:
+            out["class_names"] = [str(c) for c in names]
+        if return_assignments:
+            out["vertices"] = [int(v) for v in vertices]
+            out["assignments"] = km.last_fit.assign[:, out["best_restart"]].tolist()
+        return out
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

@@ -55,7 +55,9 @@ extern "C" {
                              *    the whole table score above it or tie with it -- the filtered rank without a score matrix)
                              *    + clane_probe_forward_*, clane_probe_grad_*, clane_probe_loss_ws_len,
                              *    clane_probe_grad_ws_len (node classification: F stacked soft-max regressions on rows of the
-                             *    table, loss / gradient / arg-max fused into the logits' contraction) */
+                             *    table, loss / gradient / arg-max fused into the logits' contraction)
+                             *    + clane_kmeans_assign_*, clane_kmeans_update_*, clane_kmeans_update_ws_len (node clustering:
+                             *    batched k-means on rows of the table, the arg-min fused into the distances' contraction) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -585,6 +587,39 @@ int clane_probe_grad_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int6
                           const float *G, int32_t K, float *ws, float *dW, float *db, void *stream);
 int64_t clane_probe_loss_ws_len(int64_t n, int32_t F);
 int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d);
+
+/* ---- node clustering (csrc/kmeans.h) ----------------------------------------------------------------------------------
+ * One Lloyd iteration of k-means for R restarts at once on the rows `rows[0..n)` of the table Z (an index outside
+ * [0, table_rows) reads as a zero row).  centres [R, K, d] and csq [R, K] = |c|^2 in the accumulate type, R, K >= 1.
+ *
+ * assign: assign[i, r] = argmin_j (csq[r, j] - 2 z_i . c[r, j]) (int32, [n, ld_assign >= R]), value ascending, ties to the
+ *   lowest centre; best[i, r] = that minimum (accumulate type, [n, ld_best >= R]) -- the squared distance without |z_i|^2,
+ *   which the caller adds.  The n x K distances never reach memory.  R <= 65535.
+ * update: order [R n] (int32): for each restart in turn the n TABLE ROWS of its list sorted by assigned centre (stably: a
+ *   centre's rows in list order); seg [R K + 1] (int64): segment offsets into order, non-decreasing, seg[R K] = R n.
+ *   centres_new[r, j] = (sum of segment r K + j's rows) / count -- the sum in a fixed order, one IEEE division -- or
+ *   centres_old[r, j], bit for bit, where the segment is empty; csq_new[r, j] = |centres_new[r, j]|^2.
+ *   ws: clane_kmeans_update_ws_len(n, R, K, d) elements of the accumulate type.
+ * No atomics: two calls give the same bits, and a restart's results do not depend on the other restarts of the call. */
+int clane_kmeans_assign_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const float *centres, const float *csq, int32_t R, int32_t K, int32_t *assign,
+                            int64_t ld_assign, float *best, int64_t ld_best, void *stream);
+int clane_kmeans_assign_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const double *centres, const double *csq, int32_t R, int32_t K, int32_t *assign,
+                            int64_t ld_assign, double *best, int64_t ld_best, void *stream);
+int clane_kmeans_assign_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const float *centres, const float *csq, int32_t R, int32_t K, int32_t *assign,
+                             int64_t ld_assign, float *best, int64_t ld_best, void *stream);
+int clane_kmeans_update_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,
+                            const int64_t *seg, int64_t n, int32_t R, int32_t K, const float *centres_old, float *ws,
+                            float *centres_new, float *csq_new, void *stream);
+int clane_kmeans_update_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,
+                            const int64_t *seg, int64_t n, int32_t R, int32_t K, const double *centres_old, double *ws,
+                            double *centres_new, double *csq_new, void *stream);
+int clane_kmeans_update_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,
+                             const int64_t *seg, int64_t n, int32_t R, int32_t K, const float *centres_old, float *ws,
+                             float *centres_new, float *csq_new, void *stream);
+int64_t clane_kmeans_update_ws_len(int64_t n, int32_t R, int32_t K, int32_t d);
 
 #ifdef __cplusplus
 }
