@@ -17,6 +17,12 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
+def item_stats(stats, slot, scores):
+    """What a class item leaves for the rescale pass: stats[2 * slot] = {max, sum of exp(score - max)} of its edges."""
+    stats[2 * slot] = scores.max()
+    stats[2 * slot + 1] = torch.exp(scores - scores.max()).sum()
+
+
 class OracleKernels(KernelBackend):
     """Implements the whole ``KernelBackend`` contract (the abstract base refuses to instantiate otherwise), so the
     engine never has to ask whether a call exists."""
@@ -89,6 +95,8 @@ class OracleKernels(KernelBackend):
             elif mode == 1:
                 dots = dots / (sq[src].sqrt() * sq[cols].sqrt())
             scores[a:b] = dots
+            if fuse_softmax and stats is not None:
+                item_stats(stats, int(item_slot[k]), dots)
         if fuse_softmax:
             rp = _np(rowptr)
             for r in class_rows.tolist():
@@ -106,10 +114,19 @@ class OracleKernels(KernelBackend):
             view /= sq[rows].sqrt() * sq[colidx[rp[0]:rp[-1]].long()].sqrt()
 
     def segment_softmax(self, rowptr, nrows, vals, min_degree=0, max_degree=0, long_rows=None):
-        rp = _np(rowptr[:nrows + 1])
-        for r in range(nrows):
-            if rp[r + 1] - rp[r] > min_degree:
-                vals[rp[r]:rp[r + 1]] = torch.softmax(vals[rp[r]:rp[r + 1]], 0)
+        """The contract of include/clane_hip.h: rows with min_degree < deg <= max_degree (0 = no upper limit) by the
+        one-wave pass, which max_degree <= min_degree (both > 0) disables; the listed rows with deg > min_degree by the
+        workgroup pass; every other row -- an unlisted long one too -- stays as it is."""
+        n_long = 0 if long_rows is None else long_rows.numel()
+        if min_degree < 0 or max_degree < 0 or (n_long and max_degree <= 0):
+            raise ValueError("segment_softmax: negative argument, or long_rows without max_degree")
+        rp = _np(rowptr)
+        one_wave = not (0 < max_degree <= min_degree)
+        rows = [r for r in range(nrows) if one_wave and rp[r + 1] - rp[r] > min_degree
+                and (max_degree == 0 or rp[r + 1] - rp[r] <= max_degree)]
+        rows += [r for r in (long_rows.tolist() if n_long else []) if rp[r + 1] - rp[r] > min_degree]
+        for r in rows:
+            vals[rp[r]:rp[r + 1]] = torch.softmax(vals[rp[r]:rp[r + 1]], 0)
 
     def make_mirror(self, row_ptr, slot, bufs):
         return (row_ptr, slot, [bufs] if isinstance(bufs, torch.Tensor) else list(bufs))

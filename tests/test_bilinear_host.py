@@ -19,7 +19,7 @@ from clane_amd.xcd import xcd_class
 from oracle import clane_oracle as O
 
 from .conftest import load_golden, write_data_root
-from .oracle_kernels import OracleKernels
+from .oracle_kernels import OracleKernels, item_stats
 from .thread_comm import ThreadWorld
 
 GOLD = "g13_karate_asym_d16.npz"
@@ -96,6 +96,8 @@ class BilinearOracleKernels(OracleKernels):
             cols = colidx[a:b].long()
             assert bool((xcd_class(cols) == (k // items_per_block) % 8).all()) and int(rw[k]) in listed
             scores[a:b] = (S[row0 + int(rw[k]), :d].unsqueeze(0) * N[cols, :d]).sum(1)
+            if fuse_softmax and stats is not None:
+                item_stats(stats, int(item_slot[k]), scores[a:b])
         if fuse_softmax:
             rp = rowptr.cpu().numpy()
             for r in class_rows.tolist():
