@@ -60,13 +60,20 @@ def embedding(args):
             raise NotImplementedError("link_evaluation runs on one GPU only; several GPUs are out of scope")
         if not isinstance(link_eval, dict) or "pairs" not in link_eval:
             raise ValueError("link_evaluation: the section needs 'pairs', the file of held-out src<TAB>dst lines")
-    # optional section (extension): node_classification: {labels: Y, ratios: [..], runs: 10, seed: 0, l2: 1.0, baseline: true}
+    # optional section (extension): node_classification: {labels: Y, ratios: [..], runs: 10, seed: 0, l2: 1.0, baseline: true,
+    # multilabel: true, predict: top_k | threshold}
     node_cls = hparams.get("node_classification") if isinstance(hparams, dict) else None
     if node_cls is not None:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:                    # before any work, as link_evaluation
             raise NotImplementedError("node_classification runs on one GPU only; several GPUs are out of scope")
         if not isinstance(node_cls, dict) or "labels" not in node_cls:
             raise ValueError("node_classification: the section needs 'labels', the file of id<TAB>class lines")
+        if not isinstance(node_cls.get("multilabel", False), bool):
+            raise ValueError(f"node_classification: multilabel must be true or false, got {node_cls['multilabel']!r}")
+        if node_cls.get("predict", "top_k") not in ("top_k", "threshold"):
+            raise ValueError(f"node_classification: predict must be top_k or threshold, got {node_cls['predict']!r}")
+        if "predict" in node_cls and not node_cls.get("multilabel", False):
+            raise ValueError("node_classification: predict belongs to multilabel: true")
     # optional section (extension): node_clustering: {labels: Y, clusters: 7, restarts: 10, seed: 0, max_iter: 300,
     # baseline: true, assignments: true}
     node_clu = hparams.get("node_clustering") if isinstance(hparams, dict) else None
@@ -179,7 +186,9 @@ def embedding(args):
         labels_file = Path(node_cls["labels"])
         if not labels_file.is_absolute():
             labels_file = Path(args.data_root) / labels_file
-        kw = {key: node_cls[key] for key in ("ratios", "runs", "seed", "l2") if key in node_cls}
+        kw = {key: node_cls[key] for key in ("ratios", "runs", "seed", "l2", "multilabel", "predict") if key in node_cls}
+        if not kw.get("multilabel", False):
+            kw.pop("multilabel", None)
         tables = {"Z": g.evaluate_labels(labels_file, table="Z", **kw)}
         if node_cls.get("baseline", False):
             tables["X"] = g.evaluate_labels(labels_file, table="X", **kw)
@@ -189,6 +198,9 @@ def embedding(args):
             json.dump({"labels": str(labels_file), "labelled": first["labelled"], "class_names": first["class_names"],
                        "ratios": [r["ratio"] for r in first["rows"]], "runs": first["runs"], "seed": first["seed"],
                        "l2": first["l2"],
+                       **({"multilabel": True, "predict": first["predict"],
+                           "constant_columns": {name: t["constant_columns"] for name, t in tables.items()}}
+                          if first.get("multilabel") else {}),
                        "tables": {name: {"rows": t["rows"], "fits": t["fits"], "skipped_fits": t["skipped_fits"]}
                                   for name, t in tables.items()}}, io, indent=1)
             io.write("\n")

@@ -99,10 +99,13 @@ for _s in ("f32", "f64"):
 SIGNATURES["clane_pair_labels"] = (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p])
 PROBE_MAX_CLASSES = 64              # CLANE_PROBE_MAX_CLASSES
 PROBE_WRITE_G, PROBE_WRITE_PRED = 1, 2
+PROBE_PRED_TOPK = 4                 # CLANE_PROBE_PRED_TOPK (one-vs-rest probe only)
 for _s in ("f32", "f64", "bf16"):   # node classification probe (csrc/label_probe.h)
     SIGNATURES[f"clane_probe_forward_{_s}"] = (
         C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p])
     SIGNATURES[f"clane_probe_grad_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p])
+    SIGNATURES[f"clane_probe_forward_ovr_{_s}"] = (      # multi-label probe (csrc/multilabel_probe.h)
+        C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p])
 SIGNATURES["clane_probe_loss_ws_len"] = (_i64, [_i64, _i32])
 SIGNATURES["clane_probe_grad_ws_len"] = (_i64, [_i64, _i32, _i32])
 for _s in ("f32", "f64", "bf16"):   # node clustering (csrc/kmeans.h)
@@ -118,6 +121,14 @@ def probe_padded_classes(C_: int) -> int:
     if not 2 <= int(C_) <= PROBE_MAX_CLASSES:
         raise ValueError(f"the label probe handles 2..{PROBE_MAX_CLASSES} classes, got {C_}")
     return 1 << (int(C_) - 1).bit_length()
+
+
+def ovr_padded_classes(C_: int) -> int:
+    """Cp of the one-vs-rest probe: as ``probe_padded_classes``, but one class is a problem too (1..64)."""
+    if not 1 <= int(C_) <= PROBE_MAX_CLASSES:
+        raise ValueError(f"the multi-label probe handles 1..{PROBE_MAX_CLASSES} classes, got {C_}")
+    return 1 << (int(C_) - 1).bit_length()
+
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
 _ACC = {torch.float32: torch.float32, torch.float64: torch.float64, torch.bfloat16: torch.float32}
@@ -436,6 +447,16 @@ class KernelBackend(abc.ABC):
         W_f^T + bias_f) against y[i] (float64 [F]); with ``G`` also G[i, f Cp + c] = split (p_c - [c == y_i]), with
         ``pred`` (int32, [n, >= F]) the arg-max class of EVERY row, ties to the lowest class."""
         raise NotImplementedError(f"{type(self).__name__} has no probe_forward")
+
+    def probe_forward_ovr(self, Z, d: int, rows, ymask, split, W, bias, col_state, F: int, C: int, max_labels: int,
+                          loss_ws, loss, G=None, pred=None, top_k: bool = True):
+        """The one-vs-rest forward of the multi-label probe.  ymask int64 [n]: the bits of the row's class set (bit c:
+        class c; the tensor holds the uint64 pattern); col_state int8 [F * Cp]: 0 fitted, -1 / +1 constant-negative /
+        -positive.  loss[f] = sum over the rows that train fit f and its fitted columns of softplus(l) - y l (float64 [F]);
+        with ``G`` also G[i, f Cp + c] = sigmoid(l) - y there and 0 elsewhere; with ``pred`` (int64, [n, >= F]) the mask
+        of predicted classes of EVERY row: ``top_k`` the popcount(ymask[i]) columns of highest value (l, or -inf / +inf
+        for a constant column; ties to the lowest class, -inf and NaN never), else the columns of value > 0."""
+        raise NotImplementedError(f"{type(self).__name__} has no probe_forward_ovr")
 
     def probe_grad_ws_len(self, n: int, K: int, d: int) -> int:
         raise NotImplementedError(f"{type(self).__name__} has no probe_grad_ws_len")
@@ -937,6 +958,36 @@ class HipKernels(KernelBackend):
         self._invoke(self._fn("clane_probe_forward", Z.dtype), "clane_probe_forward",
                      zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), _vec(y, torch.int32, "y"), n, sp, lds,
                      _vec(W, acc, "W"), _vec(bias, acc, "bias"), F, C, flags, gp, _vec(loss_ws, torch.float64, "loss_ws"),
+                     _vec(loss, torch.float64, "loss"), pp, ldp, self._stream(Z))
+
+    def probe_forward_ovr(self, Z, d: int, rows, ymask, split, W, bias, col_state, F: int, C: int, max_labels: int,
+                          loss_ws, loss, G=None, pred=None, top_k: bool = True):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        K = F * ovr_padded_classes(C)
+        sp, lds = _mat(split, "split")
+        if split.dtype != torch.uint8 or split.shape[0] < n or split.shape[1] < F or ymask.numel() != n:
+            raise ValueError("probe_forward_ovr: split must be uint8 [n, >= F], ymask one mask per row")
+        if tuple(W.shape) != (K, d) or bias.numel() != K or col_state.numel() != K:
+            raise ValueError(f"probe_forward_ovr: W must be [F * Cp, d] = [{K}, {d}], bias and col_state [{K}], got "
+                             f"{tuple(W.shape)}, {tuple(bias.shape)}, {tuple(col_state.shape)}")
+        if loss.numel() < F or loss_ws.numel() < self.probe_loss_ws_len(n, F):
+            raise ValueError("probe_forward_ovr: loss needs F doubles, loss_ws probe_loss_ws_len(n, F)")
+        flags, gp, pp, ldp = 0, None, None, 0
+        if G is not None:
+            if G.numel() < n * K:
+                raise ValueError("probe_forward_ovr: G needs n * K elements")
+            flags, gp = flags | PROBE_WRITE_G, _vec(G, acc, "G")
+        if pred is not None:
+            pp, ldp = _mat(pred, "pred")
+            if pred.dtype != torch.int64 or pred.shape[0] < n or pred.shape[1] < F:
+                raise ValueError("probe_forward_ovr: pred must be int64 [n, >= F]")
+            flags |= PROBE_WRITE_PRED | (PROBE_PRED_TOPK if top_k else 0)
+        self._invoke(self._fn("clane_probe_forward_ovr", Z.dtype), "clane_probe_forward_ovr",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), _vec(ymask, torch.int64, "ymask"), n, sp, lds,
+                     _vec(W, acc, "W"), _vec(bias, acc, "bias"), _vec(col_state, torch.int8, "col_state"), F, C,
+                     int(max_labels), flags, gp, _vec(loss_ws, torch.float64, "loss_ws"),
                      _vec(loss, torch.float64, "loss"), pp, ldp, self._stream(Z))
 
     def probe_grad(self, Z, d: int, rows, G, ws, dW, db):

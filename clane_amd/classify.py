@@ -14,6 +14,11 @@ reads arbitrary rows of the table.
 Two things differ from ``tools/evaluate_f1.py`` on purpose: the splits are a seeded torch permutation, not scikit-learn's
 ``train_test_split`` stream, and the optimiser is this module's L-BFGS, not scipy's -- the objective, its minimum and
 the F1 definitions are the same.
+
+Multi-label data (a SET of classes per vertex: BlogCatalog, Flickr, PPI, Wikipedia POS) is opt-in: ``multilabel=True``
+switches to DeepWalk's protocol -- one-vs-rest logistic regressions on the same stacked weights with the sigmoid epilogue
+of csrc/multilabel_probe.h, and for a test vertex with k true classes the k classes of highest score.  Class sets travel
+as 64-bit masks in int64 tensors (bit c: class c), predictions too.
 """
 from __future__ import annotations
 
@@ -32,10 +37,14 @@ G_BUDGET_BYTES = 8 << 30            # the [n, Fg * Cp] soft-max gradient of one 
 
 
 # ---- labels, splits, metrics: host side -------------------------------------------------------------------------
-def read_labels(path: Path, vertex_ids: Sequence[str]) -> Tuple[List[int], List[int], List[str]]:
+def read_labels(path: Path, vertex_ids: Sequence[str], multilabel: bool = False):
     """(vertices, y, classes) of the ``id<TAB>class`` lines of ``path`` (empty lines skipped): any subset of the vertices
     in any order; an id resolves as in the ``E`` file (first occurrence in ``V``).  An unknown or repeated id and a
-    malformed line are a ValueError naming the line.  Classes are indexed in sorted order."""
+    malformed line are a ValueError naming the line.  Classes are indexed in sorted order.
+
+    ``multilabel=True``: a repeated id ADDS a class to the vertex (a repeated (id, class) pair is a ValueError naming
+    the line); the return is (vertices, masks, classes) with the vertices in order of first appearance and ``masks`` one
+    Python int per vertex, bit c set for class c.  More than 64 classes are a ValueError."""
     first = {}
     for i, vid in enumerate(vertex_ids):
         first.setdefault(str(vid), i)
@@ -50,14 +59,27 @@ def read_labels(path: Path, vertex_ids: Sequence[str]) -> Tuple[List[int], List[
             vid, name = parts
             if vid not in first:
                 raise ValueError(f"labels line {n + 1}: {vid!r} is not in list")
-            if vid in seen:
-                raise ValueError(f"labels line {n + 1}: {vid!r} was labelled on line {seen[vid]} already")
-            seen[vid] = n + 1
+            if multilabel:
+                if (vid, name) in seen:
+                    raise ValueError(f"labels line {n + 1}: {vid!r} was given class {name!r} on line "
+                                     f"{seen[(vid, name)]} already")
+                seen[(vid, name)] = n + 1
+            else:
+                if vid in seen:
+                    raise ValueError(f"labels line {n + 1}: {vid!r} was labelled on line {seen[vid]} already")
+                seen[vid] = n + 1
             vertices.append(first[vid])
             names.append(name)
     classes = sorted(set(names))
     index = {c: i for i, c in enumerate(classes)}
-    return vertices, [index[c] for c in names], classes
+    if not multilabel:
+        return vertices, [index[c] for c in names], classes
+    if len(classes) > _hip.PROBE_MAX_CLASSES:
+        raise ValueError(f"labels: {len(classes)} classes; the multi-label probe handles at most {_hip.PROBE_MAX_CLASSES}")
+    masks = {}                                              # dicts keep the order of first appearance
+    for v, name in zip(vertices, names):
+        masks[v] = masks.get(v, 0) | (1 << index[name])
+    return list(masks), list(masks.values()), classes
 
 
 def index_classes(labels: Sequence) -> Tuple[List[int], list]:
@@ -113,6 +135,76 @@ def confusion_counts(y: torch.Tensor, pred: torch.Tensor, test: torch.Tensor, C:
     return torch.bincount(key[test], minlength=F * C * C).view(F, C, C)
 
 
+# ---- multi-label: class sets as 64-bit masks -----------------------------------------------------------------------
+def label_masks(sets_or_masks, C: int) -> torch.Tensor:
+    """int64 [n] on the CPU, bit c of entry i set where row i has class c (the uint64 pattern: class 63 is the sign bit).
+    ``sets_or_masks``: an integer tensor of masks, or per row a collection of class indices in [0, C) or an int mask."""
+    if not 1 <= int(C) <= _hip.PROBE_MAX_CLASSES:
+        raise ValueError(f"the multi-label probe handles 1..{_hip.PROBE_MAX_CLASSES} classes (C > 64 is out of scope), "
+                         f"got {C}")
+    if isinstance(sets_or_masks, torch.Tensor):
+        if sets_or_masks.dtype.is_floating_point or sets_or_masks.dtype == torch.bool:
+            raise ValueError("label_masks: a tensor must hold integer masks")
+        out = sets_or_masks.detach().cpu().to(torch.int64).reshape(-1).clone()
+    else:
+        values = []
+        for i, item in enumerate(sets_or_masks):
+            if isinstance(item, int):
+                m = item
+            else:
+                m = 0
+                for c in item:
+                    c = int(c)
+                    if not 0 <= c < C:
+                        raise ValueError(f"label_masks: row {i}: class {c} is not in [0, {C})")
+                    m |= 1 << c
+            if not 0 <= m < (1 << 64):
+                raise ValueError(f"label_masks: row {i}: {m} is no 64-bit mask")
+            values.append(m - (1 << 64) if m >= (1 << 63) else m)
+        out = torch.tensor(values, dtype=torch.int64)
+    if C < 64 and out.numel() and bool(((out >> C) != 0).any()):
+        raise ValueError(f"label_masks: a mask has a bit at or above C = {C}")
+    return out
+
+
+def mask_bits(masks: torch.Tensor, C: int) -> torch.Tensor:
+    """bool [..., C]: bit c of every mask."""
+    return ((masks.unsqueeze(-1) >> torch.arange(C, device=masks.device)) & 1).bool()
+
+
+def column_states(masks: torch.Tensor, split: torch.Tensor, C: int) -> torch.Tensor:
+    """int8 [F, C] from masks [n] and split [n, F]: 0 a column to fit; -1 where no training row of the fit has the class
+    (or nothing trains the fit); +1 where every training row has it."""
+    trains = (split != 0).double()
+    pos = trains.T @ mask_bits(masks, C).double()                       # [F, C]: counts, exact in float64
+    n_train = trains.sum(0)[:, None]
+    state = torch.zeros(pos.shape, dtype=torch.int8, device=pos.device)
+    state[pos == n_train] = 1
+    state[pos == 0] = -1                                                # also n_train == 0
+    return state
+
+
+def multilabel_counts(masks: torch.Tensor, pred: torch.Tensor, test: torch.Tensor, C: int) -> torch.Tensor:
+    """int64 [F, C, 3] = (tp, fp, fn) per fit and class over the fit's test rows, from masks [n], pred [n, F] (masks)
+    and the test mask [n, F], by integer bit operations."""
+    y, p = masks.to(pred.device)[:, None], pred
+    keep = torch.where(test, torch.full_like(p, -1), torch.zeros_like(p))        # all bits / none
+    count = lambda m: mask_bits(m & keep, C).to(torch.int64).sum(0)     # noqa: E731
+    return torch.stack([count(y & p), count(~y & p), count(y & ~p)], dim=-1)
+
+
+def f1_from_counts(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(micro, macro) F1 of (tp, fp, fn) counts [..., C, 3], as scikit-learn's ``f1_score`` gives on indicator matrices
+    with ``zero_division=0``: micro = 2 sum TP / (2 sum TP + sum FP + sum FN); macro = the mean over ALL C classes of
+    2 TP / (2 TP + FP + FN), a class with an empty denominator counting 0.  float64."""
+    c = counts.double()
+    num, den = 2.0 * c[..., 0], 2.0 * c[..., 0] + c[..., 1] + c[..., 2]
+    f1 = torch.where(den > 0, num / den.clamp(min=1.0), torch.zeros_like(den))
+    sden = den.sum(-1)
+    micro = torch.where(sden > 0, num.sum(-1) / sden.clamp(min=1.0), torch.zeros_like(sden))
+    return micro, f1.mean(-1)
+
+
 # ---- tables (shared with cluster.KMeans) --------------------------------------------------------------------------
 def table_and_rows(eng, vertices, table: str = "Z"):
     """(table, int32 rows) for vertex indices: the current embeddings ("Z") or the content embeddings ("X")."""
@@ -145,6 +237,8 @@ class ProbeFit:
     skipped: torch.Tensor       # [F] bool: fewer than 2 classes among the training rows -- not fitted
     pred: torch.Tensor          # [n, F] int32: arg-max class of EVERY row under fit f
     n_train: torch.Tensor       # [F] int64
+    constant: Optional[torch.Tensor] = None     # fit_multilabel: [F] int64, the constant (not fitted) class columns;
+    #                                             pred then holds int64 masks, bit c = class c predicted
 
 
 class LabelProbe:
@@ -202,6 +296,87 @@ class LabelProbe:
         if n and (int(y.min()) < 0 or int(y.max()) >= C):
             raise ValueError(f"fit: classes must be in [0, {C})")
         split = split.to(dev).contiguous()
+        pred = torch.zeros(n, F, dtype=torch.int32, device=dev)
+        trains = split != 0
+        n_train = trains.sum(0)
+        onehot = torch.zeros(n, C, dtype=torch.float64, device=dev)
+        onehot[torch.arange(n, device=dev), y.long()] = 1.0
+        classes_seen = ((trains.double().T @ onehot) > 0).sum(1)        # [F]: classes among a fit's training rows
+        skipped = classes_seen < 2
+
+        def forward(a, b, Wg, bg, loss_ws, loss, G, want_pred):
+            k.probe_forward(Z, d, rows, y, split[:, a:b], Wg, bg, b - a, C, loss_ws, loss,
+                            G=G, pred=pred[:, a:b] if want_pred else None)
+
+        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward)
+        nw = Cp * d
+        W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
+        b = x[:, nw:][:, :C].to(acc).contiguous()
+        return ProbeFit(W=W, b=b, objective=J, grad_max=gmax, iterations=iterations,
+                        converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train)
+
+    def fit_multilabel(self, Z: torch.Tensor, rows: torch.Tensor, masks: torch.Tensor, split: torch.Tensor, C: int,
+                       predict: str = "top_k") -> ProbeFit:
+        """One-vs-rest: every column of ``split`` fits one binary logistic regression per class on the rows ``rows``,
+        whose class sets are ``masks`` (int64 [n], bit c: class c -- ``label_masks``).  The objective is ``J_f`` with the
+        sum of the fitted columns' binary cross-entropies in place of the soft-max cross-entropy; it is separable over
+        the classes, so its minimiser is ``OneVsRestClassifier(LogisticRegression(C=1 / l2))``'s on the fitted columns.
+        A column whose class no / every training row of the fit has is constant: not fitted, weights 0, predicted never
+        / always, and counted in ``constant``.  A fit without a fitted column is ``skipped``.  ``pred`` holds int64 masks
+        of EVERY row: ``predict="top_k"`` gives a row with k true classes the k classes of highest logit (ties to the
+        lowest class; a constant-positive column first, a constant-negative one never), ``"threshold"`` the classes of
+        logit > 0."""
+        if predict not in ("top_k", "threshold"):
+            raise ValueError(f"predict must be 'top_k' or 'threshold', got {predict!r}")
+        if not 1 <= int(C) <= _hip.PROBE_MAX_CLASSES:
+            raise ValueError(f"the multi-label probe handles 1..{_hip.PROBE_MAX_CLASSES} classes (C > 64 is out of "
+                             f"scope), got {C}")
+        eng, k = self.eng, self.k
+        dev, d = Z.device, eng.d
+        acc = _hip.acc_dtype(Z.dtype)
+        Cp = _hip.ovr_padded_classes(C)
+        n, F = int(rows.numel()), int(split.shape[1]) if split.dim() == 2 else 0
+        if split.dtype != torch.uint8 or split.dim() != 2 or split.shape[0] != n or masks.numel() != n or F < 1:
+            raise ValueError("fit_multilabel: split must be uint8 [n, F] and masks hold one class set per row")
+        if masks.dtype != torch.int64:
+            raise ValueError("fit_multilabel: masks must be int64 (label_masks)")
+        rows = rows.to(dev, torch.int32).contiguous()
+        masks = masks.to(dev).reshape(-1).contiguous()
+        if C < 64 and n and bool(((masks >> C) != 0).any()):
+            raise ValueError(f"fit_multilabel: a mask has a bit at or above C = {C}")
+        split = split.to(dev).contiguous()
+        pred = torch.zeros(n, F, dtype=torch.int64, device=dev)
+        n_train = (split != 0).sum(0)
+        states = column_states(masks, split, C)                         # [F, C]
+        col_state = torch.zeros(F, Cp, dtype=torch.int8, device=dev)    # pad columns: ignored by the kernel
+        col_state[:, :C] = states
+        col_state = col_state.reshape(-1)
+        constant = (states != 0).sum(1)
+        skipped = constant == C
+        max_labels = int(mask_bits(masks, C).sum(1).max()) if n else 0
+        top_k = predict == "top_k"
+
+        def forward(a, b, Wg, bg, loss_ws, loss, G, want_pred):
+            k.probe_forward_ovr(Z, d, rows, masks, split[:, a:b], Wg, bg, col_state[a * Cp:b * Cp], b - a, C, max_labels,
+                                loss_ws, loss, G=G, pred=pred[:, a:b] if want_pred else None, top_k=top_k)
+
+        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward)
+        nw = Cp * d
+        W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
+        b = x[:, nw:][:, :C].to(acc).contiguous()
+        return ProbeFit(W=W, b=b, objective=J, grad_max=gmax, iterations=iterations,
+                        converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train,
+                        constant=constant)
+
+    def _minimise(self, Z, rows, F: int, Cp: int, skipped, n_train, forward):
+        """The batched L-BFGS both probes share: (x [F, Cp (d + 1)], J, grad_max, iterations), then one last pass that
+        writes the predictions.  ``forward(a, b, Wg, bg, loss_ws, loss, G, want_pred)`` makes the forward kernel call for
+        the fits [a, b) of one group: the losses into ``loss`` [b - a], d loss / d logits into ``G`` unless it is None,
+        the predictions where ``want_pred``."""
+        eng, k = self.eng, self.k
+        dev, d = Z.device, eng.d
+        acc = _hip.acc_dtype(Z.dtype)
+        n = int(rows.numel())
         groups = self.groups(n, F, Cp, acc)
         Fg = max(b - a for a, b in groups)
         G = torch.empty(n * Fg * Cp, dtype=acc, device=dev)
@@ -209,16 +384,9 @@ class LabelProbe:
         grad_ws = torch.empty(k.probe_grad_ws_len(n, Fg * Cp, d), dtype=acc, device=dev)
         dW = torch.empty(Fg * Cp * d, dtype=acc, device=dev)
         db = torch.empty(Fg * Cp, dtype=acc, device=dev)
-        pred = torch.zeros(n, F, dtype=torch.int32, device=dev)
         self.passes = {"forward": 0, "grad": 0}
         nw, P = Cp * d, Cp * (d + 1)
 
-        trains = split != 0
-        n_train = trains.sum(0)
-        onehot = torch.zeros(n, C, dtype=torch.float64, device=dev)
-        onehot[torch.arange(n, device=dev), y.long()] = 1.0
-        classes_seen = ((trains.double().T @ onehot) > 0).sum(1)        # [F]: classes among a fit's training rows
-        skipped = classes_seen < 2
         n_f = n_train.clamp(min=1).double()
 
         def evaluate(x, want_grad, which=None, want_pred=False):
@@ -231,8 +399,7 @@ class LabelProbe:
                     continue
                 Wg = x[a:b, :nw].reshape((b - a) * Cp, d).to(acc).contiguous()
                 bg = x[a:b, nw:].reshape(-1).to(acc).contiguous()
-                k.probe_forward(Z, d, rows, y, split[:, a:b], Wg, bg, b - a, C, loss_ws, loss[a:b],
-                                G=G if want_grad else None, pred=pred[:, a:b] if want_pred else None)
+                forward(a, b, Wg, bg, loss_ws, loss[a:b], G if want_grad else None, want_pred)
                 self.passes["forward"] += 1
                 if want_grad:
                     Kg = (b - a) * Cp
@@ -327,34 +494,47 @@ class LabelProbe:
             done = done | (gmax <= self.gtol) | (failed & ~retry) | (iterations >= self.max_iter)
 
         evaluate(x, False, None, want_pred=True)
-        W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
-        b = x[:, nw:][:, :C].to(acc).contiguous()
-        return ProbeFit(W=W, b=b, objective=J, grad_max=gmax, iterations=iterations,
-                        converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train)
+        return x, J, gmax, iterations
 
     # ---- the experiment -----------------------------------------------------------------------------------------
     def evaluate(self, vertices, y, n_classes: Optional[int] = None, ratios: Sequence[float] = DEFAULT_RATIOS,
-                 runs: int = 10, seed: int = 0, table: str = "Z") -> dict:
+                 runs: int = 10, seed: int = 0, table: str = "Z", multilabel: bool = False,
+                 predict: str = "top_k") -> dict:
         """The README's table for the labelled vertices (vertex indices, classes in [0, n_classes)): per ratio the mean
-        micro / macro F1 on the test rows over the runs whose training rows hold at least 2 classes."""
+        micro / macro F1 on the test rows over the runs whose training rows hold at least 2 classes.
+
+        ``multilabel=True``: ``y`` holds a class SET per vertex (``label_masks``' forms), the fits are one-vs-rest
+        (``fit_multilabel``), F1 is scikit-learn's on indicator matrices, a run is used unless it has no fitted column,
+        and the result also carries ``"multilabel"``, ``"predict"`` and ``"constant_columns"``."""
         Z, rows = self.table_and_rows(vertices, table)
-        y = torch.as_tensor(y, dtype=torch.int64).reshape(-1)
-        C = int(n_classes) if n_classes is not None else int(y.max()) + 1
         n = rows.numel()
-        if y.numel() != n:
-            raise ValueError("evaluate: one class per labelled vertex")
-        split, fits = make_splits(n, ratios, runs, seed)
-        fit = self.fit(Z, rows, y, split, C)
-        split_d = split.to(Z.device)
-        conf = confusion_counts(y.to(Z.device), fit.pred, split_d == 0, C)
-        micro, macro = f1_from_confusion(conf)
+        if multilabel:
+            if n_classes is None:
+                raise ValueError("evaluate: multilabel needs n_classes")
+            C = int(n_classes)
+            y = label_masks(y, C)
+            if y.numel() != n:
+                raise ValueError("evaluate: one class set per labelled vertex")
+            split, fits = make_splits(n, ratios, runs, seed)
+            fit = self.fit_multilabel(Z, rows, y, split, C, predict=predict)
+            micro, macro = f1_from_counts(multilabel_counts(y.to(Z.device), fit.pred, split.to(Z.device) == 0, C))
+        else:
+            y = torch.as_tensor(y, dtype=torch.int64).reshape(-1)
+            C = int(n_classes) if n_classes is not None else int(y.max()) + 1
+            if y.numel() != n:
+                raise ValueError("evaluate: one class per labelled vertex")
+            split, fits = make_splits(n, ratios, runs, seed)
+            fit = self.fit(Z, rows, y, split, C)
+            split_d = split.to(Z.device)
+            conf = confusion_counts(y.to(Z.device), fit.pred, split_d == 0, C)
+            micro, macro = f1_from_confusion(conf)
         used = (~fit.skipped).double()
         per_ratio = lambda v: (v * used).view(len(ratios), runs).sum(1)     # noqa: E731
         n_used = per_ratio(torch.ones_like(used))
         mean = lambda v: (per_ratio(v) / n_used.clamp(min=1.0)).tolist()    # noqa: E731
         micro_r, macro_r, n_used = mean(micro), mean(macro), n_used.tolist()
         nan = float("nan")
-        return {
+        out = {
             "table": table, "labelled": n, "classes": C, "l2": self.l2, "seed": int(seed), "runs": int(runs),
             "rows": [{"ratio": float(r), "micro_f1": micro_r[i] if n_used[i] else nan,
                       "macro_f1": macro_r[i] if n_used[i] else nan, "runs_used": int(n_used[i])}
@@ -365,3 +545,7 @@ class LabelProbe:
                      "micro_f1": micro.tolist(), "macro_f1": macro.tolist()},
             "skipped_fits": int(fit.skipped.sum()),
         }
+        if multilabel:
+            out["fits"]["constant_columns"] = fit.constant.tolist()
+            out.update(multilabel=True, predict=predict, constant_columns=int(fit.constant.sum()))
+        return out

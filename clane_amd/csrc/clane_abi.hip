@@ -14,6 +14,7 @@
 #include "device_utils.h"
 #include "kmeans.h"
 #include "label_probe.h"
+#include "multilabel_probe.h"
 #include "link_eval.h"
 #include "link_rank.h"
 #include "pair_train.h"
@@ -768,6 +769,45 @@ int probe_forward(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const 
     return check_launch("probe_forward");
 }
 
+// One-vs-rest probe (multilabel_probe.h): the same launch shape, the sigmoid / top-k epilogue.
+template <typename T, typename A>
+int probe_forward_ovr(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, const uint64_t *ymask,
+                      int64_t n, const uint8_t *split, int64_t ld_split, const A *W, const A *bias, const int8_t *col_state,
+                      int32_t F, int32_t C, int32_t max_labels, int32_t flags, A *G, double *loss_ws, double *loss,
+                      uint64_t *pred, int64_t ld_pred, void *stream) {
+    static_assert(kOvrWriteG == CLANE_PROBE_WRITE_G && kOvrWritePred == CLANE_PROBE_WRITE_PRED &&
+                      kOvrPredTopk == CLANE_PROBE_PRED_TOPK,
+                  "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d,
+            "probe_forward_ovr: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    REQUIRE(C >= 1 && C <= kProbeMaxClasses, "probe_forward_ovr: C must be in [1, %d], got %d", kProbeMaxClasses, C);
+    REQUIRE(max_labels >= 0 && max_labels <= C, "probe_forward_ovr: max_labels must be in [0, C = %d], got %d", C,
+            max_labels);
+    const int cp_log = probe_cp_log(C);
+    REQUIRE(F >= 1 && F <= (INT32_MAX >> 7), "probe_forward_ovr: bad number of fits %d", F);
+    REQUIRE(ld_split >= F, "probe_forward_ovr: ld_split %lld < F = %d", (long long)ld_split, F);
+    REQUIRE((flags & ~(CLANE_PROBE_WRITE_G | CLANE_PROBE_WRITE_PRED | CLANE_PROBE_PRED_TOPK)) == 0,
+            "probe_forward_ovr: unknown flags %d", flags);
+    REQUIRE(!(flags & CLANE_PROBE_WRITE_PRED) || ld_pred >= F, "probe_forward_ovr: ld_pred %lld < F = %d",
+            (long long)ld_pred, F);
+    REQUIRE(loss_ws && loss, "probe_forward_ovr: null loss workspace/output");
+    REQUIRE(n == 0 || (Z && rows && ymask && split && W && bias && col_state), "probe_forward_ovr: null pointer");
+    REQUIRE(n == 0 || !(flags & CLANE_PROBE_WRITE_G) || G, "probe_forward_ovr: CLANE_PROBE_WRITE_G needs G");
+    REQUIRE(n == 0 || !(flags & CLANE_PROBE_WRITE_PRED) || pred, "probe_forward_ovr: CLANE_PROBE_WRITE_PRED needs pred");
+    const int K = F << cp_log;
+    const int n_tiles = int(ceil_div(int64_t(K), int64_t(kProjBN)));
+    const int64_t row_tiles = n > 0 ? probe_row_tiles(n) : 0;
+    const int64_t blocks = row_tiles * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "probe_forward_ovr: %lld rows x %d fits is too many for one launch", (long long)n, F);
+    if (blocks > 0)
+        probe_forward_ovr_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, ymask, n, split, ld_split, W, bias, col_state, F, C, cp_log, max_labels, flags, G,
+            loss_ws, pred, ld_pred, n_tiles);
+    probe_loss_reduce_kernel<<<unsigned(F), kBlock, 0, (hipStream_t)stream>>>(loss_ws, row_tiles, F, loss);
+    return check_launch("probe_forward_ovr");
+}
+
 template <typename T, typename A>
 int probe_grad(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *G,
                int32_t K, A *ws, A *dW, A *db, void *stream) {
@@ -1214,6 +1254,15 @@ int clane_rank_merge_f64(const double *cand_score, const int32_t *cand_id, int64
                                   double *loss, int32_t *pred, int64_t ld_pred, void *stream) {                        \
         return probe_forward<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, y, n, split, ld_split,   \
                                     W, bias, F, C, flags, G, loss_ws, loss, pred, ld_pred, stream);                    \
+    }                                                                                                                  \
+    int clane_probe_forward_ovr_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,    \
+                                      const uint64_t *ymask, int64_t n, const uint8_t *split, int64_t ld_split,        \
+                                      const AT *W, const AT *bias, const int8_t *col_state, int32_t F, int32_t C,      \
+                                      int32_t max_labels, int32_t flags, AT *G, double *loss_ws, double *loss,         \
+                                      uint64_t *pred, int64_t ld_pred, void *stream) {                                 \
+        return probe_forward_ovr<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, ymask, n, split,     \
+                                        ld_split, W, bias, col_state, F, C, max_labels, flags, G, loss_ws, loss, pred, \
+                                        ld_pred, stream);                                                              \
     }                                                                                                                  \
     int clane_probe_grad_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,           \
                                int64_t n, const AT *G, int32_t K, AT *ws, AT *dW, AT *db, void *stream) {              \

@@ -510,7 +510,7 @@ class Graph(torch.utils.data.Dataset):
         return LinkRanker(eng, similarity).evaluate(src, dst, hits, filter_existing).as_dict()
 
     def evaluate_labels(self, labels, ratios=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), runs: int = 10, seed: int = 0,
-                        l2: float = 1.0, table: str = "Z") -> dict:
+                        l2: float = 1.0, table: str = "Z", multilabel: bool = False, predict: str = "top_k") -> dict:
         """The reference README's node-classification table for the CURRENT embeddings (extension): a soft-max regression
         on the labelled vertices' rows per (train share, random split), all fits at once on the GPU (classify.py), micro
         and macro F1 on each fit's test rows, averaged over the runs of a share.  ``labels``: a file of ``id<TAB>class``
@@ -518,10 +518,19 @@ class Graph(torch.utils.data.Dataset):
         are indexed in sorted order.  ``table="X"`` probes the content embeddings instead (the README's bag-of-words
         row).  Returns ``{"table", "labelled", "classes", "class_names", "rows": [{"ratio", "micro_f1", "macro_f1",
         "runs_used"}], "fits": {...per fit: ratio, run, iterations, converged, objective, skipped, micro_f1, macro_f1},
-        ...}``.  Several GPUs and a column division raise NotImplementedError."""
+        ...}``.  Several GPUs and a column division raise NotImplementedError.
+
+        ``multilabel=True`` (DeepWalk's protocol for BlogCatalog-like data): a vertex has a SET of classes -- in the file
+        a repeated id adds a class, in the Python forms every entry is a collection of classes -- at most 64 in all; the
+        fits are one-vs-rest logistic regressions, and a test vertex with k true classes is given the k classes of
+        highest score (``predict="top_k"``) or those of positive score (``"threshold"``).  The result also has
+        ``"multilabel"``, ``"predict"`` and ``"constant_columns"`` (class columns of a fit that no or every training
+        vertex has: not fitted, predicted never / always)."""
         from .classify import LabelProbe, index_classes, read_labels
+        if predict not in ("top_k", "threshold"):
+            raise ValueError(f"evaluate_labels: predict must be 'top_k' or 'threshold', got {predict!r}")
         if isinstance(labels, (str, Path)):
-            vertices, y, names = read_labels(Path(labels), self.vertex_ids)
+            vertices, y, names = read_labels(Path(labels), self.vertex_ids, multilabel=bool(multilabel))
         else:
             if isinstance(labels, tuple) and len(labels) == 2:
                 vertices, raw = list(labels[0]), list(labels[1])
@@ -530,10 +539,21 @@ class Graph(torch.utils.data.Dataset):
                 vertices = list(range(len(self)))
             if len(raw) != len(vertices):
                 raise ValueError("evaluate_labels: one class per labelled vertex")
-            raw = [c.item() if isinstance(c, torch.Tensor) else c for c in raw]
-            y, names = index_classes(raw)
+            item = lambda c: c.item() if isinstance(c, torch.Tensor) else c     # noqa: E731
+            if multilabel:
+                if any(isinstance(s, (str, bytes)) or not hasattr(s, "__iter__") for s in raw):
+                    raise ValueError("evaluate_labels: multilabel needs a collection of classes per labelled vertex")
+                sets = [[item(c) for c in s] for s in raw]
+                names = sorted({c for s in sets for c in s})
+                if len(names) > 64:
+                    raise ValueError(f"evaluate_labels: {len(names)} classes; the multi-label probe handles at most 64")
+                index = {c: i for i, c in enumerate(names)}
+                y = [sum(1 << index[c] for c in set(s)) for s in sets]
+            else:
+                y, names = index_classes([item(c) for c in raw])
+        kw = dict(multilabel=True, predict=predict) if multilabel else {}
         out = LabelProbe(self.engine(), l2=l2).evaluate(vertices, y, len(names), ratios=tuple(ratios), runs=runs,
-                                                        seed=seed, table=table)
+                                                        seed=seed, table=table, **kw)
         out["class_names"] = [str(c) for c in names]
         return out
 

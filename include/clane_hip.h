@@ -57,7 +57,10 @@ extern "C" {
                              *    clane_probe_grad_ws_len (node classification: F stacked soft-max regressions on rows of the
                              *    table, loss / gradient / arg-max fused into the logits' contraction)
                              *    + clane_kmeans_assign_*, clane_kmeans_update_*, clane_kmeans_update_ws_len (node clustering:
-                             *    batched k-means on rows of the table, the arg-min fused into the distances' contraction) */
+                             *    batched k-means on rows of the table, the arg-min fused into the distances' contraction)
+                             *    + clane_probe_forward_ovr_* (multi-label node classification: F stacked one-vs-rest
+                             *    regressions, sigmoid loss / gradient and the top-k label masks fused into the logits'
+                             *    contraction; workspaces and clane_probe_grad_* as for the soft-max probe) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -587,6 +590,37 @@ int clane_probe_grad_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int6
                           const float *G, int32_t K, float *ws, float *dW, float *db, void *stream);
 int64_t clane_probe_loss_ws_len(int64_t n, int32_t F);
 int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d);
+
+/* ---- multi-label probe (csrc/multilabel_probe.h) -----------------------------------------------------------------------
+ * F one-vs-rest logistic regressions per class on the same stacked layout (W [K, d], bias [K], K = F * Cp, Cp = C rounded up
+ * to a power of two), 1 <= C <= CLANE_PROBE_MAX_CLASSES.  ymask [n] (uint64): bit c set where row i has class c.
+ * col_state [K] (int8): 0 a fitted column, -1 / +1 a column whose class no / every training row of its fit has (pad
+ * columns: ignored).  With l the logit, y the row's bit and "live" = split[i, f] != 0 and col_state == 0:
+ *   loss[f] = sum over live (i, c) of softplus(l) - y l            (always; double; loss_ws: probe_loss_ws_len doubles)
+ *   G[i, f Cp + c] = sigmoid(l) - y where live, else 0              (CLANE_PROBE_WRITE_G; G is [n, K] contiguous)
+ *   pred[i, f] = a uint64 mask of predicted classes, every row      (CLANE_PROBE_WRITE_PRED; pred is [n, ld_pred >= F])
+ *     a column's value is l, -inf (state -1) or +inf (state +1); without CLANE_PROBE_PRED_TOPK bit c is set iff the value
+ *     is > 0; with it a row with k = popcount(ymask[i]) <= max_labels classes gets the k columns of highest value, ties to
+ *     the lowest class, a NaN or -inf value never (so fewer than k bits may be set).  0 <= max_labels <= C bounds the
+ *     rounds: it must be at least the largest popcount of ymask.
+ * The gradient of the weights is clane_probe_grad_* on this G.  No atomics: two calls give the same bits, and a fit's results
+ * do not depend on the other fits of the call. */
+#define CLANE_PROBE_PRED_TOPK 4
+int clane_probe_forward_ovr_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                                const uint64_t *ymask, int64_t n, const uint8_t *split, int64_t ld_split, const float *W,
+                                const float *bias, const int8_t *col_state, int32_t F, int32_t C, int32_t max_labels,
+                                int32_t flags, float *G, double *loss_ws, double *loss, uint64_t *pred, int64_t ld_pred,
+                                void *stream);
+int clane_probe_forward_ovr_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                                const uint64_t *ymask, int64_t n, const uint8_t *split, int64_t ld_split, const double *W,
+                                const double *bias, const int8_t *col_state, int32_t F, int32_t C, int32_t max_labels,
+                                int32_t flags, double *G, double *loss_ws, double *loss, uint64_t *pred, int64_t ld_pred,
+                                void *stream);
+int clane_probe_forward_ovr_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                                 const uint64_t *ymask, int64_t n, const uint8_t *split, int64_t ld_split, const float *W,
+                                 const float *bias, const int8_t *col_state, int32_t F, int32_t C, int32_t max_labels,
+                                 int32_t flags, float *G, double *loss_ws, double *loss, uint64_t *pred, int64_t ld_pred,
+                                 void *stream);
 
 /* ---- node clustering (csrc/kmeans.h) ----------------------------------------------------------------------------------
  * One Lloyd iteration of k-means for R restarts at once on the rows `rows[0..n)` of the table Z (an index outside
