@@ -2,8 +2,8 @@
 //
 //   kmeans_assign : per (row i of the list, restart r) the centre j that minimises csq[r, j] - 2 z_i . c[r, j] (the
 //                   squared distance without the row's own |z_i|^2, which no centre changes) and that minimum.  The
-//                   dots are project_rows_kernel's MFMA tile (projection.h) with the A operand's rows taken through
-//                   `rows`, as probe_forward_kernel does; a workgroup owns 128 rows of ONE restart and walks every
+//                   dots are mfma_tile_product's (mfma_tile.h) with the A operand's rows taken through `rows`; a
+//                   workgroup owns 128 rows of ONE restart and walks every
 //                   128-column tile of that restart's centres, keeping the running (best, id) of its rows in registers.
 //                   The n x K distances never reach memory.
 //   kmeans_update : centre = (sum of its segment's rows) / count, from the rows sorted by assigned centre.  The
@@ -11,7 +11,7 @@
 //
 // Order rule of the arg-min: value ascending, ties by centre index ascending -- a total order, so what a row gets does
 // not depend on which tile, wave or lane met a centre first.  A (row, centre) dot is the same MFMA chain in
-// projection.h's k order wherever the pair falls in the tiling, so two calls give the same bits and a restart gets the
+// mfma_slice's k order (mfma_tile.h) wherever the pair falls in the tiling, so two calls give the same bits and a restart gets the
 // same bits whatever else shares the call.
 //
 // Sums of the update run in a fixed order (no atomics): a segment is cut into chunks of kKmChunk rows counted from the
@@ -24,7 +24,7 @@
 #include <climits>
 
 #include "device_utils.h"
-#include "projection.h"
+#include "mfma_tile.h"
 
 namespace clane {
 
@@ -54,36 +54,22 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 8 ? 1 : 2) void kmeans_assign_
     const T *__restrict__ Z, int64_t table_rows, int d, int64_t ldz, const int32_t *__restrict__ rows, int64_t n,
     const A *__restrict__ centres, const A *__restrict__ csq, int K, int32_t *__restrict__ assign, int64_t ld_assign,
     A *__restrict__ best, int64_t ld_best) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int PER = BM * BK / kBlock;
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    constexpr int BM = Tile::BM, BN = Tile::BN;
+    __shared__ __attribute__((aligned(16))) A As[BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[BN * Tile::LD];
     __shared__ A Sv[2][BM];
     __shared__ int Sj[2][BM];
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const Tile t(threadIdx.x);
+    const int tid = threadIdx.x;
     const int64_t m0 = int64_t(blockIdx.x) * BM;
     const int rst = blockIdx.y;
     const A *__restrict__ Cr = centres + int64_t(rst) * K * d;
     const A *__restrict__ cq = csq + int64_t(rst) * K;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
 
-    const int sk = tid % BK, si = tid / BK;
-    int64_t roff[PER];                                    // gathered rows of this thread's staging slots; < 0: none
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int64_t r = m0 + si + s * (kBlock / BK);
-        int64_t t = -1;
-        if (r < n) {
-            t = rows[r];
-            if (t >= table_rows) t = -1;
-        }
-        roff[s] = t < 0 ? -1 : t * ldz;
-    }
+    int64_t roff[Tile::PER_A];                            // gathered rows of this thread's staging slots; < 0: none
+    mfma_gather_offsets(rows, m0, n, table_rows, ldz, roff);
 
     const A inf = __builtin_huge_val();
     A bv[4][4];                                           // [mi][reg]: running minimum of 16 rows over this lane's columns
@@ -97,52 +83,19 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 8 ? 1 : 2) void kmeans_assign_
         }
 
     for (int n0 = 0; n0 < K; n0 += BN) {
-        A ra[PER], rb[PER];
-        auto fetch = [&](int k0) {
-            const int k = k0 + sk;
-#pragma unroll
-            for (int s = 0; s < PER; ++s) {
-                const int j = n0 + si + s * (kBlock / BK);
-                ra[s] = (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0);
-                rb[s] = (k < d && j < K) ? Cr[int64_t(j) * d + k] : A(0);
-            }
-        };
-        acc4 acc[4][4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
-
-        fetch(0);
-        for (int k0 = 0; k0 < d; k0 += BK) {
-            __syncthreads();                              // the previous slice (or tile) has been read by every wave
-#pragma unroll
-            for (int s = 0; s < PER; ++s) {
-                const int i = si + s * (kBlock / BK);
-                As[i * LD + sk] = ra[s];
-                Bs[i * LD + sk] = rb[s];
-            }
-            __syncthreads();
-            if (k0 + BK < d) fetch(k0 + BK);
-            A a[4][4], b[4][4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                    b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-                }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-        }
+        typename Tile::acc4 acc[4][4];
+        mfma_zero<A>(acc);
+        mfma_tile_product(
+            t, As, Bs, d, acc,
+            [&](int s, int, int k) { return (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0); },
+            [&](int, int i, int k) {
+                const int j = n0 + i;
+                return (k < d && j < K) ? Cr[int64_t(j) * d + k] : A(0);
+            });
         // a lane holds column n0 + wn + 16 ni + li of 16 rows; pad columns count as +inf: they are never taken
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
-            const int col = n0 + wn + 16 * ni + li;
+            const int col = n0 + t.col(ni);
             if (col < K) {
                 const A cc = cq[col];
 #pragma unroll
@@ -162,10 +115,10 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 8 ? 1 : 2) void kmeans_assign_
             km_xor_step<4>(bv[mi][reg], bj[mi][reg]);
             km_xor_step<2>(bv[mi][reg], bj[mi][reg]);
             km_xor_step<1>(bv[mi][reg], bj[mi][reg]);
-            if (li == 0) {
-                const int i = wm + 16 * mi + M::row(lane, reg);
-                Sv[wave >> 1][i] = bv[mi][reg];
-                Sj[wave >> 1][i] = bj[mi][reg];
+            if (t.li == 0) {
+                const int i = t.row(mi, reg);
+                Sv[t.wn / 64][i] = bv[mi][reg];
+                Sj[t.wn / 64][i] = bj[mi][reg];
             }
         }
     __syncthreads();

@@ -22,8 +22,8 @@
 #include <climits>
 
 #include "device_utils.h"
+#include "mfma_tile.h"
 #include "pair_train.h"
-#include "projection.h"
 
 namespace clane {
 
@@ -60,9 +60,52 @@ __device__ __forceinline__ void probe_fit_reduce(V (&v)[4], int Cp, Op op) {
     }
 }
 
+// What a lane knows about its four columns n0 + wn + 16 ni + li of W_all: the fit, the class within the fit, whether the
+// column exists (col < K) and is a real class of its fit (not padding up to Cp), and its bias.
+template <typename A>
+struct ProbeCols {
+    int fit[4], cls[4];
+    bool in_k[4], real[4];
+    A bcol[4];
+    __device__ __forceinline__ ProbeCols(const MfmaTile<A, 4> &t, int n0, int K, int C, int cp_log,
+                                         const A *__restrict__ bias) {
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const int col = n0 + t.col(ni);
+            fit[ni] = col >> cp_log;
+            cls[ni] = col & ((1 << cp_log) - 1);
+            in_k[ni] = col < K;
+            real[ni] = in_k[ni] && cls[ni] < C;
+            bcol[ni] = in_k[ni] ? bias[col] : A(0);
+        }
+    }
+};
+
+// The tile's loss per fit from lsum[ni], a lane's sum over its 16 rows in (mi, reg) order: the four row groups of the
+// wave, then the two waves that share the columns.  loss_ws [row tiles, F].  Every thread of the workgroup calls it.
+template <typename A>
+__device__ __forceinline__ void probe_tile_loss(const MfmaTile<A, 4> &t, const double (&lsum)[4],
+                                                double (&Ls)[kWavesPerBlock][kWave], int n0, int K, int F, int cp_log,
+                                                int64_t row_tile, double *__restrict__ loss_ws) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+        double v = lsum[ni];
+        v += lane_xor<16>(v);
+        v += lane_xor<32>(v);
+        if (t.g == 0) Ls[tid / kWave][16 * ni + t.li] = v;
+    }
+    __syncthreads();
+    if (tid < kProjBN) {
+        const int col = n0 + tid, q = tid / 64, within = tid % 64;
+        if (col < K && (col & ((1 << cp_log) - 1)) == 0)
+            loss_ws[row_tile * F + (col >> cp_log)] = Ls[2 * q][within] + Ls[2 * q + 1][within];
+    }
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------
-// The tiling of project_rows_kernel (projection.h) with the rows of the A operand taken through `rows`, as
-// pair_project_kernel does, and n_out = K.  Block b: column tile b % n_tiles of row tile b / n_tiles.  loss_ws
+// mfma_tile_product (mfma_tile.h) with the rows of the A operand taken through `rows` and n_out = K.  Block b: column
+// tile b % n_tiles of row tile b / n_tiles.  loss_ws
 // [row tiles, F]: the tile's sum of split * (lse - logit[y]) per fit, in double.  split is [n, >= F] with leading
 // dimension ld_split, pred [n, >= F] with ld_pred: a caller that fits in groups hands in a column slice of each.
 template <typename T, typename A>
@@ -71,93 +114,33 @@ __global__ __launch_bounds__(kBlock) void probe_forward_kernel(
     const int32_t *__restrict__ y, int64_t n, const uint8_t *__restrict__ split, int64_t ld_split,
     const A *__restrict__ W, const A *__restrict__ bias, int F, int C, int cp_log, int flags, A *__restrict__ G,
     double *__restrict__ loss_ws, int32_t *__restrict__ pred, int64_t ld_pred, int n_tiles) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int PER = BM * BK / kBlock;
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    __shared__ __attribute__((aligned(16))) A As[Tile::BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[Tile::BN * Tile::LD];
     __shared__ double Ls[kWavesPerBlock][kWave];
 
     const int Cp = 1 << cp_log, K = F << cp_log;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const Tile t(threadIdx.x);
     const int64_t tile = blockIdx.x;
-    const int n0 = int(tile % n_tiles) * BN;
-    const int64_t row_tile = tile / n_tiles, m0 = row_tile * BM;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
+    const int n0 = int(tile % n_tiles) * Tile::BN;
+    const int64_t row_tile = tile / n_tiles, m0 = row_tile * Tile::BM;
 
-    const int sk = tid % BK, si = tid / BK;
-    int64_t roff[PER];                                    // gathered rows of this thread's staging slots; < 0: none
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int64_t r = m0 + si + s * (kBlock / BK);
-        int64_t t = -1;
-        if (r < n) {
-            t = rows[r];
-            if (t >= table_rows) t = -1;
-        }
-        roff[s] = t < 0 ? -1 : t * ldz;
-    }
-    A ra[PER], rb[PER];
-    auto fetch = [&](int k0) {
-        const int k = k0 + sk;
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int j = n0 + si + s * (kBlock / BK);
-            ra[s] = (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0);
-            rb[s] = (k < d && j < K) ? W[int64_t(j) * d + k] : A(0);
-        }
-    };
+    int64_t roff[Tile::PER_A];                               // gathered rows of this thread's staging slots; < 0: none
+    mfma_gather_offsets(rows, m0, n, table_rows, ldz, roff);
 
-    acc4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
-
-    fetch(0);
-    for (int k0 = 0; k0 < d; k0 += BK) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int i = si + s * (kBlock / BK);
-            As[i * LD + sk] = ra[s];
-            Bs[i * LD + sk] = rb[s];
-        }
-        __syncthreads();
-        if (k0 + BK < d) fetch(k0 + BK);
-        A a[4][4], b[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-            }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-    }
+    typename Tile::acc4 acc[4][4];
+    mfma_zero<A>(acc);
+    mfma_tile_product(
+        t, As, Bs, d, acc,
+        [&](int s, int, int k) { return (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0); },
+        [&](int, int i, int k) {
+            const int j = n0 + i;
+            return (k < d && j < K) ? W[int64_t(j) * d + k] : A(0);
+        });
 
     // ---- epilogue: a lane holds column n0 + wn + 16 ni + li of 16 rows; the 16 lanes of one g share a row ----------
     const A neg_inf = -__builtin_huge_val();
-    int fit[4], cls[4];
-    bool in_k[4], real[4];
-    A bcol[4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        const int col = n0 + wn + 16 * ni + li;
-        fit[ni] = col >> cp_log;
-        cls[ni] = col & (Cp - 1);
-        in_k[ni] = col < K;
-        real[ni] = in_k[ni] && cls[ni] < C;
-        bcol[ni] = in_k[ni] ? bias[col] : A(0);
-    }
+    const ProbeCols<A> pc(t, n0, K, C, cp_log, bias);
     double lsum[4] = {0.0, 0.0, 0.0, 0.0};
     auto op_max = [](A u, A v) { return u > v ? u : v; };
     auto op_add = [](A u, A v) { return u + v; };
@@ -166,56 +149,42 @@ __global__ __launch_bounds__(kBlock) void probe_forward_kernel(
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int64_t r = m0 + wm + 16 * mi + M::row(lane, reg);
+            const int64_t r = m0 + t.row(mi, reg);
             const bool in_n = r < n;
             const int yr = in_n ? y[r] : -1;
             A l[4], mx[4], e[4], se[4], ly[4];
             int am[4];
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
-                l[ni] = acc[mi][ni][reg] + bcol[ni];
-                mx[ni] = real[ni] ? l[ni] : neg_inf;
+                l[ni] = acc[mi][ni][reg] + pc.bcol[ni];
+                mx[ni] = pc.real[ni] ? l[ni] : neg_inf;
             }
             probe_fit_reduce(mx, Cp, op_max);
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
-                e[ni] = real[ni] ? exp_acc<A>(l[ni] - mx[ni]) : A(0);
+                e[ni] = pc.real[ni] ? exp_acc<A>(l[ni] - mx[ni]) : A(0);
                 se[ni] = e[ni];
-                ly[ni] = (real[ni] && cls[ni] == yr) ? l[ni] : A(0);
-                am[ni] = (real[ni] && l[ni] == mx[ni]) ? cls[ni] : INT_MAX;      // ties: the lowest class
+                ly[ni] = (pc.real[ni] && pc.cls[ni] == yr) ? l[ni] : A(0);
+                am[ni] = (pc.real[ni] && l[ni] == mx[ni]) ? pc.cls[ni] : INT_MAX;      // ties: the lowest class
             }
             probe_fit_reduce(se, Cp, op_add);
             probe_fit_reduce(ly, Cp, op_add);
             probe_fit_reduce(am, Cp, op_min);
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
-                if (!(in_n && in_k[ni])) continue;
-                const int col = n0 + wn + 16 * ni + li;
-                const bool trains = split[r * ld_split + fit[ni]] != 0;
+                if (!(in_n && pc.in_k[ni])) continue;
+                const int col = n0 + t.col(ni);
+                const bool trains = split[r * ld_split + pc.fit[ni]] != 0;
                 if (flags & kProbeWriteG) {
                     A gv = A(0);
-                    if (trains && real[ni]) gv = e[ni] / se[ni] - (cls[ni] == yr ? A(1) : A(0));
+                    if (trains && pc.real[ni]) gv = e[ni] / se[ni] - (pc.cls[ni] == yr ? A(1) : A(0));
                     G[r * int64_t(K) + col] = gv;
                 }
                 if (trains) lsum[ni] += double(mx[ni] + log_acc<A>(se[ni]) - ly[ni]);
-                if ((flags & kProbeWritePred) && cls[ni] == 0) pred[r * ld_pred + fit[ni]] = am[ni];
+                if ((flags & kProbeWritePred) && pc.cls[ni] == 0) pred[r * ld_pred + pc.fit[ni]] = am[ni];
             }
         }
-    // the tile's loss per fit: a lane's 16 rows (above, in (mi, reg) order), the four row groups of the wave, then the
-    // two waves that share the columns
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        double t = lsum[ni];
-        t += lane_xor<16>(t);
-        t += lane_xor<32>(t);
-        if (g == 0) Ls[wave][16 * ni + li] = t;
-    }
-    __syncthreads();
-    if (tid < BN) {
-        const int col = n0 + tid, q = tid / 64, within = tid % 64;
-        if (col < K && (col & (Cp - 1)) == 0)
-            loss_ws[row_tile * F + (col >> cp_log)] = Ls[2 * q][within] + Ls[2 * q + 1][within];
-    }
+    probe_tile_loss(t, lsum, Ls, n0, K, F, cp_log, row_tile, loss_ws);
 }
 
 // loss[f] = the sum over the row tiles, in tile order within a thread's slice and the slices in a fixed order.
@@ -238,8 +207,8 @@ __global__ __launch_bounds__(kBlock) void probe_loss_reduce_kernel(const double 
 
 // ---- backward --------------------------------------------------------------------------------------------------
 // Partial dW of one chunk of rows: out[o, c] = sum_i G[i, o] Z[rows[i], c] -- pair_grad_kernel's scheme (the A operand
-// is G^T, the B operand the gathered rows of Z, both staged k-contiguous per output row; memory is row-major in i, so
-// a thread stages one o / c of 8 rows of each 16-row slice).  blockIdx = (tile of dW: K tiles x d tiles, chunk).  The
+// is G^T, the B operand the gathered rows of Z, mfma_tile_product_transposed).  blockIdx = (tile of dW: K tiles x d
+// tiles, chunk).  The
 // workgroups of the first d tile also sum their G columns: a thread adds what it stages, in row order, and the two
 // threads of a column are added at the end -- db's partial.  The partials of chunk z go to ws + z * K * (d + 1):
 // [K, d] of dW, then [K] of db.
@@ -248,88 +217,39 @@ __global__ __launch_bounds__(kBlock) void probe_grad_kernel(const T *__restrict_
                                                             int64_t ldz, const int32_t *__restrict__ rows, int64_t n,
                                                             const A *__restrict__ G, int K, A *__restrict__ ws,
                                                             int n_tiles) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int KS = kBlock / BM;                       // rows of a slice staged side by side (2)
-    constexpr int PER = BK / KS;                          // rows per thread and slice (8)
-    static_assert(BM == BN && kBlock % BM == 0 && BK % KS == 0 && kGradChunk % BK == 0, "staging layout");
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    constexpr int BM = Tile::BM, KS = Tile::KS;
+    static_assert(kGradChunk % Tile::BK == 0, "a chunk is whole slices");
+    __shared__ __attribute__((aligned(16))) A As[Tile::BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[Tile::BN * Tile::LD];
     __shared__ A Db[KS][BM];
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int o0 = int(blockIdx.x / n_tiles) * BM, i0 = int(blockIdx.x % n_tiles) * BN;
+    const Tile t(threadIdx.x);
+    const int o0 = int(blockIdx.x / n_tiles) * Tile::BM, i0 = int(blockIdx.x % n_tiles) * Tile::BN;
     const int64_t kbeg = int64_t(blockIdx.y) * kGradChunk;
     const int64_t kend = kbeg + kGradChunk < n ? kbeg + kGradChunk : n;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
 
-    const int so = tid % BM, sk = tid / BM;
+    const int so = int(threadIdx.x) % BM, sk = int(threadIdx.x) / BM;     // the staged row / column, the k lane
     const bool o_ok = o0 + so < K, i_ok = i0 + so < d;
-    A ra[PER], rb[PER];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int64_t k = k0 + sk + KS * s;
-            ra[s] = A(0);
-            rb[s] = A(0);
-            if (k < kend) {
-                int64_t t = rows[k];
-                if (t >= table_rows) t = -1;
-                if (o_ok) ra[s] = G[k * K + o0 + so];
-                if (i_ok && t >= 0) rb[s] = A(Elem<T>::to_acc(Z[t * ldz + i0 + so]));
-            }
-        }
-    };
 
-    acc4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
+    typename Tile::acc4 acc[4][4];
+    mfma_zero<A>(acc);
     A dbs = A(0);
-
-    fetch(kbeg);
-    for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            As[so * LD + sk + KS * s] = ra[s];
-            Bs[so * LD + sk + KS * s] = rb[s];
-            dbs += ra[s];
-        }
-        __syncthreads();
-        if (k0 + BK < kend) fetch(k0 + BK);
-        A a[4][4], b[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-            }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-    }
+    mfma_tile_product_transposed(
+        t, As, Bs, kbeg, kend, acc,
+        [&](int64_t k, A &a, A &b) {
+            int64_t r = rows[k];
+            if (r >= table_rows) r = -1;
+            if (o_ok) a = G[k * K + o0 + so];
+            if (i_ok && r >= 0) b = A(Elem<T>::to_acc(Z[r * ldz + i0 + so]));
+        },
+        [&](A a) { dbs += a; });
 
     A *__restrict__ out = ws + int64_t(blockIdx.y) * K * (int64_t(d) + 1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const int i = i0 + wn + 16 * ni + li;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int o = o0 + wm + 16 * mi + M::row(lane, reg);
-                if (o < K && i < d) out[int64_t(o) * d + i] = acc[mi][ni][reg];
-            }
-        }
+    mfma_for_each(t, acc, [&](int r, int c, A v) {
+        const int o = o0 + r, i = i0 + c;
+        if (o < K && i < d) out[int64_t(o) * d + i] = v;
+    });
     if (i0 == 0) {                                        // uniform over the workgroup
         Db[sk][so] = dbs;
         __syncthreads();

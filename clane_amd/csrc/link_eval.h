@@ -2,8 +2,8 @@
 // table, how many eligible candidates score above the target, how many tie with it on either side of its label, and
 // how many are eligible at all (rank_count_kernel).  From the counts the host forms the filtered rank, MRR, Hits@K, AUC.
 //
-// The smaller sibling of rank_scores_kernel (link_rank.h): the same tiling, the same MFMA chain in projection.h's k
-// order, the same scaling (acc * rq) * cs -- so a pair scores the SAME BITS here as in the top-k lists, and
+// The smaller sibling of rank_scores_kernel (link_rank.h): the same tiling, the same MFMA chain in mfma_slice's k
+// order (mfma_tile.h), the same scaling (acc * rq) * cs -- so a pair scores the SAME BITS here as in the top-k lists, and
 // 1 + greater + equal_lower is the target's place in top_k's order (score descending, ties by label ascending).  The
 // insertion is replaced by counting, which has no writer turns and no lists.
 //
@@ -27,10 +27,13 @@
 #include "device_utils.h"
 #include "edge_score.h"
 #include "link_rank.h"
-#include "projection.h"
+#include "mfma_tile.h"
 
 namespace clane {
 
+// Like rank_scores_kernel, rank_count_kernel keeps its own text of the staged k loop (through the shared loop it measured
+// slower at the largest shape: profiles/r13_mfma_tile_times.md); mfma_slice (mfma_tile.h) is the contract for its k
+// order: step kk gives lane group g = lane / 16 the k index 4 g + kk, and the MFMAs run in the order kk, mi, ni.
 #ifndef CLANE_COUNT_MIN_WAVES
 #define CLANE_COUNT_MIN_WAVES 2   // rank_count_kernel: __launch_bounds__ 2nd argument (waves per SIMD)
 #endif

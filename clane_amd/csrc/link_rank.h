@@ -6,12 +6,12 @@
 // (Phi_src z_u) . (Phi_dst z_v) of AsymmertricSimilarity (similarity.py:40-57; S = Y, N = Y + d of the projected table,
 // projection.h) or the cosine of CosineSimilarity (similarity.py:26-37; S = N = Z, the modes of edge_score.h).
 //
-// rank_scores_kernel is project_rows_kernel's tiling (projection.h) with the A operand's rows taken through the query
-// list (as pair_project_kernel does) and the B operand the rows of N with a leading dimension: a 256-thread workgroup
+// rank_scores_kernel is mfma_tile.h's contraction with the A operand's rows taken through the query list and the B
+// operand the rows of N with a leading dimension: a 256-thread workgroup
 // owns one tile of 32 MI queries (128 for f32 / bf16, 64 for f64: the lists below have to fit the LDS beside the
 // staged slices) and one slab of candidate rows, walks the slab's 128-row tiles and keeps every query's running top-k
 // in LDS, so the Q x V score matrix never exists.  A pair's dot always is the same MFMA chain in the fixed k order of
-// projection.h -- it does not depend on the tile, the slab or the lane it falls in -- so the merged result is
+// mfma_slice -- it does not depend on the tile, the slab or the lane it falls in -- so the merged result is
 // bit-identical for every n_slabs.
 //
 // Selection, after a tile's MFMAs: every accumulator is scaled (mode) and compared with its query's current k-th score
@@ -26,7 +26,7 @@
 
 #include "device_utils.h"
 #include "edge_score.h"
-#include "projection.h"
+#include "mfma_tile.h"
 
 namespace clane {
 
@@ -88,6 +88,10 @@ constexpr size_t rank_list_bytes(int bm, int k) { return size_t(bm) * k * (sizeo
 // blockIdx.x = slab * q_tiles + query tile: the workgroups that read one slab of N run together.
 // Slab s holds the candidate tiles [s * tiles_per_slab, (s + 1) * tiles_per_slab) -- none at all when n_slabs is more
 // than the table has tiles; such a workgroup only writes its empty lists.
+// rank_scores_kernel keeps its own text of the staged k loop (through the shared loop it measured slower:
+// profiles/r13_mfma_tile_times.md).  mfma_slice (mfma_tile.h) is the contract for its k order all the same: step kk
+// gives lane group g = lane / 16 the k index 4 g + kk, and the MFMAs run in the order kk, mi, ni.  A change there is a
+// change here.
 #ifndef CLANE_RANK_MIN_WAVES
 #define CLANE_RANK_MIN_WAVES 2    // rank_scores_kernel: __launch_bounds__ 2nd argument (waves per SIMD)
 #endif

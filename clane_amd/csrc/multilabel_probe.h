@@ -43,95 +43,37 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
     const A *__restrict__ W, const A *__restrict__ bias, const int8_t *__restrict__ col_state, int F, int C, int cp_log,
     int max_labels, int flags, A *__restrict__ G, double *__restrict__ loss_ws, uint64_t *__restrict__ pred,
     int64_t ld_pred, int n_tiles) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int PER = BM * BK / kBlock;
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    __shared__ __attribute__((aligned(16))) A As[Tile::BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[Tile::BN * Tile::LD];
     __shared__ double Ls[kWavesPerBlock][kWave];
 
     const int Cp = 1 << cp_log, K = F << cp_log;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const Tile t(threadIdx.x);
     const int64_t tile = blockIdx.x;
-    const int n0 = int(tile % n_tiles) * BN;
-    const int64_t row_tile = tile / n_tiles, m0 = row_tile * BM;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
+    const int n0 = int(tile % n_tiles) * Tile::BN;
+    const int64_t row_tile = tile / n_tiles, m0 = row_tile * Tile::BM;
 
-    // ---- the main loop of probe_forward_kernel, unchanged ---------------------------------------------------------
-    const int sk = tid % BK, si = tid / BK;
-    int64_t roff[PER];                                    // gathered rows of this thread's staging slots; < 0: none
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int64_t r = m0 + si + s * (kBlock / BK);
-        int64_t t = -1;
-        if (r < n) {
-            t = rows[r];
-            if (t >= table_rows) t = -1;
-        }
-        roff[s] = t < 0 ? -1 : t * ldz;
-    }
-    A ra[PER], rb[PER];
-    auto fetch = [&](int k0) {
-        const int k = k0 + sk;
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int j = n0 + si + s * (kBlock / BK);
-            ra[s] = (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0);
-            rb[s] = (k < d && j < K) ? W[int64_t(j) * d + k] : A(0);
-        }
-    };
+    // ---- the logits, as in probe_forward_kernel --------------------------------------------------------------------
+    int64_t roff[Tile::PER_A];                            // gathered rows of this thread's staging slots; < 0: none
+    mfma_gather_offsets(rows, m0, n, table_rows, ldz, roff);
 
-    acc4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
-
-    fetch(0);
-    for (int k0 = 0; k0 < d; k0 += BK) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int i = si + s * (kBlock / BK);
-            As[i * LD + sk] = ra[s];
-            Bs[i * LD + sk] = rb[s];
-        }
-        __syncthreads();
-        if (k0 + BK < d) fetch(k0 + BK);
-        A a[4][4], b[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-            }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-    }
+    typename Tile::acc4 acc[4][4];
+    mfma_zero<A>(acc);
+    mfma_tile_product(
+        t, As, Bs, d, acc,
+        [&](int s, int, int k) { return (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0); },
+        [&](int, int i, int k) {
+            const int j = n0 + i;
+            return (k < d && j < K) ? W[int64_t(j) * d + k] : A(0);
+        });
 
     // ---- epilogue: a lane holds column n0 + wn + 16 ni + li of 16 rows; the 16 lanes of one g share a row ----------
     const A neg_inf = -__builtin_huge_val(), pos_inf = __builtin_huge_val();
-    int fit[4], cls[4], state[4];
-    bool in_k[4], real[4];
-    A bcol[4];
+    const ProbeCols<A> pc(t, n0, K, C, cp_log, bias);
+    int state[4];
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        const int col = n0 + wn + 16 * ni + li;
-        fit[ni] = col >> cp_log;
-        cls[ni] = col & (Cp - 1);
-        in_k[ni] = col < K;
-        real[ni] = in_k[ni] && cls[ni] < C;
-        bcol[ni] = in_k[ni] ? bias[col] : A(0);
-        state[ni] = real[ni] ? int(col_state[col]) : 0;
-    }
+    for (int ni = 0; ni < 4; ++ni) state[ni] = pc.real[ni] ? int(col_state[n0 + t.col(ni)]) : 0;
     double lsum[4] = {0.0, 0.0, 0.0, 0.0};
     auto op_max = [](A u, A v) { return u > v ? u : v; };
     auto op_add = [](A u, A v) { return u + v; };
@@ -141,24 +83,24 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int64_t r = m0 + wm + 16 * mi + M::row(lane, reg);
+            const int64_t r = m0 + t.row(mi, reg);
             const bool in_n = r < n;
             const uint64_t ym = in_n ? ymask[r] : uint64_t(0);
             A l[4], term[4];
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
-                l[ni] = acc[mi][ni][reg] + bcol[ni];
+                l[ni] = acc[mi][ni][reg] + pc.bcol[ni];
                 term[ni] = A(0);
-                const bool live = in_n && real[ni] && state[ni] == 0 && split[r * ld_split + fit[ni]] != 0;
+                const bool live = in_n && pc.real[ni] && state[ni] == 0 && split[r * ld_split + pc.fit[ni]] != 0;
                 A gv = A(0);
                 if (live) {
-                    const A yv = ((ym >> cls[ni]) & 1) ? A(1) : A(0);
+                    const A yv = ((ym >> pc.cls[ni]) & 1) ? A(1) : A(0);
                     const A e = exp_acc<A>(l[ni] < A(0) ? l[ni] : -l[ni]);
                     const A den = A(1) + e;
                     term[ni] = (l[ni] > A(0) ? l[ni] : A(0)) + log_acc<A>(den) - yv * l[ni];
                     gv = (l[ni] >= A(0) ? A(1) / den : e / den) - yv;
                 }
-                if ((flags & kOvrWriteG) && in_n && in_k[ni]) G[r * int64_t(K) + (n0 + wn + 16 * ni + li)] = gv;
+                if ((flags & kOvrWriteG) && in_n && pc.in_k[ni]) G[r * int64_t(K) + (n0 + t.col(ni))] = gv;
             }
             probe_fit_reduce(term, Cp, op_add);
 #pragma unroll
@@ -169,7 +111,7 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
         // bit (4 mi + reg) * 4 + ni of `open`: the lane's column ni of its row (mi, reg) can still be taken; of `sel`: it
         // is predicted.  The rounds are the outer loop, so every index into the accumulators stays a constant.
         auto value = [&](int mi, int reg, int ni) -> A {
-            return state[ni] == 0 ? A(acc[mi][ni][reg] + bcol[ni]) : (state[ni] < 0 ? neg_inf : pos_inf);
+            return state[ni] == 0 ? A(acc[mi][ni][reg] + pc.bcol[ni]) : (state[ni] < 0 ? neg_inf : pos_inf);
         };
         uint64_t open = 0, sel = 0;
 #pragma unroll
@@ -181,19 +123,19 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
                     const uint64_t bit = uint64_t(1) << ((4 * mi + reg) * 4 + ni);
                     const A v = value(mi, reg, ni);
                     if (flags & kOvrPredTopk) {
-                        if (real[ni] && v > neg_inf) open |= bit;         // NaN, -inf: never taken
+                        if (pc.real[ni] && v > neg_inf) open |= bit;         // NaN, -inf: never taken
                     } else {
-                        if (real[ni] && v > A(0)) sel |= bit;
+                        if (pc.real[ni] && v > A(0)) sel |= bit;
                     }
                 }
         if (flags & kOvrPredTopk)
-            for (int t = 0; t < max_labels; ++t) {
+            for (int round = 0; round < max_labels; ++round) {
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
-                        const int64_t r = m0 + wm + 16 * mi + M::row(lane, reg);
-                        const bool takes = r < n && __popcll(ymask[r]) > t;
+                        const int64_t r = m0 + t.row(mi, reg);
+                        const bool takes = r < n && __popcll(ymask[r]) > round;
                         A v[4], mx[4];
                         int am[4];
 #pragma unroll
@@ -204,12 +146,12 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
                         probe_fit_reduce(mx, Cp, op_max);
 #pragma unroll
                         for (int ni = 0; ni < 4; ++ni)
-                            am[ni] = (((open >> ((4 * mi + reg) * 4 + ni)) & 1) && v[ni] == mx[ni]) ? cls[ni] : INT_MAX;
+                            am[ni] = (((open >> ((4 * mi + reg) * 4 + ni)) & 1) && v[ni] == mx[ni]) ? pc.cls[ni] : INT_MAX;
                         probe_fit_reduce(am, Cp, op_min);                 // ties: the lowest class
 #pragma unroll
                         for (int ni = 0; ni < 4; ++ni) {
                             const uint64_t bit = uint64_t(1) << ((4 * mi + reg) * 4 + ni);
-                            if (takes && (open & bit) && am[ni] == cls[ni]) {
+                            if (takes && (open & bit) && am[ni] == pc.cls[ni]) {
                                 sel |= bit;
                                 open &= ~bit;
                             }
@@ -220,11 +162,11 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
-                const int64_t r = m0 + wm + 16 * mi + M::row(lane, reg);
+                const int64_t r = m0 + t.row(mi, reg);
                 int lo[4], hi[4];
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) {
-                    const uint64_t m = ((sel >> ((4 * mi + reg) * 4 + ni)) & 1) ? uint64_t(1) << cls[ni] : uint64_t(0);
+                    const uint64_t m = ((sel >> ((4 * mi + reg) * 4 + ni)) & 1) ? uint64_t(1) << pc.cls[ni] : uint64_t(0);
                     lo[ni] = int(uint32_t(m));
                     hi[ni] = int(uint32_t(m >> 32));
                 }
@@ -232,25 +174,11 @@ __global__ __launch_bounds__(kBlock, sizeof(A) == 4 ? 2 : 1) void probe_forward_
                 probe_fit_reduce(hi, Cp, op_or);
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni)
-                    if (r < n && in_k[ni] && cls[ni] == 0)
-                        pred[r * ld_pred + fit[ni]] = (uint64_t(uint32_t(hi[ni])) << 32) | uint64_t(uint32_t(lo[ni]));
+                    if (r < n && pc.in_k[ni] && pc.cls[ni] == 0)
+                        pred[r * ld_pred + pc.fit[ni]] = (uint64_t(uint32_t(hi[ni])) << 32) | uint64_t(uint32_t(lo[ni]));
             }
     }
-    // the tile's loss per fit: a lane's 16 rows (above, in (mi, reg) order), the four row groups of the wave, then the
-    // two waves that share the columns
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        double t = lsum[ni];
-        t += lane_xor<16>(t);
-        t += lane_xor<32>(t);
-        if (g == 0) Ls[wave][16 * ni + li] = t;
-    }
-    __syncthreads();
-    if (tid < BN) {
-        const int col = n0 + tid, q = tid / 64, within = tid % 64;
-        if (col < K && (col & (Cp - 1)) == 0)
-            loss_ws[row_tile * F + (col >> cp_log)] = Ls[2 * q][within] + Ls[2 * q + 1][within];
-    }
+    probe_tile_loss(t, lsum, Ls, n0, K, F, cp_log, row_tile, loss_ws);
 }
 
 }  // namespace clane

@@ -17,7 +17,7 @@
 #pragma once
 
 #include "device_utils.h"
-#include "projection.h"
+#include "mfma_tile.h"
 
 namespace clane {
 
@@ -37,101 +37,46 @@ __device__ __forceinline__ double log_acc<double>(double v) {
 
 // ---- forward ---------------------------------------------------------------------------------------------------
 // Out_side[k, 0:d) = W_side . Z[idx_side[k], 0:d)  for side 0 (src, Phi_src = W[0:d]) and side 1 (dst, Phi_dst = W[d:2d]).
-// The tiling of project_rows_kernel (projection.h) with the rows of the A operand taken through the index list and
-// n_out = d; blockIdx.y is the side.  Outputs are [B, d] contiguous.
+// mfma_tile_product (mfma_tile.h) with the rows of the A operand taken through the index list and n_out = d;
+// blockIdx.y is the side.  Outputs are [B, d] contiguous.
 template <typename T, typename A>
 __global__ __launch_bounds__(kBlock) void pair_project_kernel(const T *__restrict__ Z, int64_t table_rows, int d,
                                                               int64_t ldz, const int32_t *__restrict__ src,
                                                               const int32_t *__restrict__ dst, int64_t B,
                                                               const A *__restrict__ W, A *__restrict__ PA,
                                                               A *__restrict__ PB, int n_tiles) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int PER = BM * BK / kBlock;
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    __shared__ __attribute__((aligned(16))) A As[Tile::BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[Tile::BN * Tile::LD];
 
     const int side = blockIdx.y;
     const int32_t *__restrict__ idx = side ? dst : src;
     const A *__restrict__ Ws = W + int64_t(side) * d * d;
     A *__restrict__ Y = side ? PB : PA;
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const Tile t(threadIdx.x);
     const int64_t tile = blockIdx.x;
-    const int n0 = int(tile % n_tiles) * BN;
-    const int64_t m0 = (tile / n_tiles) * BM;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
+    const int n0 = int(tile % n_tiles) * Tile::BN;
+    const int64_t m0 = (tile / n_tiles) * Tile::BM;
 
-    const int sk = tid % BK, si = tid / BK;
-    int64_t roff[PER];                                    // gathered rows of this thread's staging slots; < 0: none
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int64_t r = m0 + si + s * (kBlock / BK);
-        int64_t t = -1;
-        if (r < B) {
-            t = idx[r];
-            if (t >= table_rows) t = -1;
-        }
-        roff[s] = t < 0 ? -1 : t * ldz;
-    }
-    A ra[PER], rb[PER];
-    auto fetch = [&](int k0) {
-        const int k = k0 + sk;
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int j = n0 + si + s * (kBlock / BK);
-            ra[s] = (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0);
-            rb[s] = (k < d && j < d) ? Ws[int64_t(j) * d + k] : A(0);
-        }
-    };
+    int64_t roff[Tile::PER_A];                               // gathered rows of this thread's staging slots; < 0: none
+    mfma_gather_offsets(idx, m0, B, table_rows, ldz, roff);
 
-    acc4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
+    typename Tile::acc4 acc[4][4];
+    mfma_zero<A>(acc);
+    mfma_tile_product(
+        t, As, Bs, d, acc,
+        [&](int s, int, int k) { return (k < d && roff[s] >= 0) ? A(Elem<T>::to_acc(Z[roff[s] + k])) : A(0); },
+        [&](int, int i, int k) {
+            const int j = n0 + i;
+            return (k < d && j < d) ? Ws[int64_t(j) * d + k] : A(0);
+        });
 
-    fetch(0);
-    for (int k0 = 0; k0 < d; k0 += BK) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int i = si + s * (kBlock / BK);
-            As[i * LD + sk] = ra[s];
-            Bs[i * LD + sk] = rb[s];
-        }
-        __syncthreads();
-        if (k0 + BK < d) fetch(k0 + BK);
-        A a[4][4], b[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-            }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-    }
-
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const int col = n0 + wn + 16 * ni + li;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int64_t r = m0 + wm + 16 * mi + M::row(lane, reg);
-                if (r < B && col < d) Y[r * d + col] = acc[mi][ni][reg];
-            }
-        }
+    mfma_for_each(t, acc, [&](int i, int j, A v) {
+        const int64_t r = m0 + i;
+        const int col = n0 + j;
+        if (r < B && col < d) Y[r * d + col] = v;
+    });
 }
 
 // ---- loss ------------------------------------------------------------------------------------------------------
@@ -182,100 +127,50 @@ __global__ __launch_bounds__(kBlock) void pair_loss_kernel(const A *__restrict__
 // ---- backward --------------------------------------------------------------------------------------------------
 // Partial dW of one chunk of pairs: side 0 (rows [0, d) of dW): out[o, i] = sum_k g_k Bm[k, o] Z[src_k, i];
 // side 1 (rows [d, 2d)): out[o, i] = sum_k g_k A[k, o] Z[dst_k, i].  A GEMM whose contraction index is the pair: the
-// A operand is (g . projected)^T, the B operand the gathered rows of Z, both staged k-contiguous per output row as
-// in projection.h.  Memory is pair-major, so a thread stages one output row / column of 8 pairs of each 16-pair
-// slice (consecutive threads: consecutive o / i of one pair -- coalesced).  blockIdx = (tile of dW's side, side,
-// chunk); the partial tile goes to ws[(chunk * 2 + side) * d * d + o * d + i].
+// A operand is (g . projected)^T, the B operand the gathered rows of Z; memory is pair-major, so the slices are staged
+// by mfma_tile_product_transposed (mfma_tile.h).  blockIdx = (tile of dW's side, side, chunk); the partial tile goes to
+// ws[(chunk * 2 + side) * d * d + o * d + i].
 template <typename T, typename A>
 __global__ __launch_bounds__(kBlock) void pair_grad_kernel(const T *__restrict__ Z, int64_t table_rows, int d,
                                                            int64_t ldz, const int32_t *__restrict__ src,
                                                            const int32_t *__restrict__ dst, int64_t B,
                                                            const A *__restrict__ PA, const A *__restrict__ PB,
                                                            const A *__restrict__ gvec, A *__restrict__ ws, int n_tiles) {
-    using M = ProjMfma<A>;
-    using acc4 = typename M::acc4;
-    constexpr int BM = kProjBM, BN = kProjBN, BK = kProjBK;
-    constexpr int LD = BK + 16 / int(sizeof(A));
-    constexpr int KS = kBlock / BM;                       // pairs of a slice staged side by side (2)
-    constexpr int PER = BK / KS;                          // pairs per thread and slice (8)
-    static_assert(BM == BN && kBlock % BM == 0 && BK % KS == 0 && kGradChunk % BK == 0, "staging layout");
-    __shared__ __attribute__((aligned(16))) A As[BM * LD];
-    __shared__ __attribute__((aligned(16))) A Bs[BN * LD];
+    using Tile = MfmaTile<A, 4>;
+    static_assert(kGradChunk % Tile::BK == 0, "a chunk is whole slices");
+    __shared__ __attribute__((aligned(16))) A As[Tile::BM * Tile::LD];
+    __shared__ __attribute__((aligned(16))) A Bs[Tile::BN * Tile::LD];
 
     const int side = blockIdx.y;
     const int32_t *__restrict__ idx = side ? dst : src;
     const A *__restrict__ Op = side ? PA : PB;
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int o0 = int(blockIdx.x / n_tiles) * BM, i0 = int(blockIdx.x % n_tiles) * BN;
+    const Tile t(threadIdx.x);
+    const int o0 = int(blockIdx.x / n_tiles) * Tile::BM, i0 = int(blockIdx.x % n_tiles) * Tile::BN;
     const int64_t kbeg = int64_t(blockIdx.z) * kGradChunk;
     const int64_t kend = kbeg + kGradChunk < B ? kbeg + kGradChunk : B;
-    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-    const int g = lane >> 4, li = lane & 15;
 
-    const int so = tid % BM, sk = tid / BM;
+    const int so = int(threadIdx.x) % Tile::BM;              // the output row / column this thread stages
     const bool o_ok = o0 + so < d, i_ok = i0 + so < d;
-    A ra[PER], rb[PER];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int64_t k = k0 + sk + KS * s;
-            ra[s] = A(0);
-            rb[s] = A(0);
-            if (k < kend) {
-                const A gk = gvec[k];
-                int64_t t = idx[k];
-                if (t >= table_rows) t = -1;
-                if (o_ok) ra[s] = gk * Op[k * d + o0 + so];
-                if (i_ok && t >= 0) rb[s] = A(Elem<T>::to_acc(Z[t * ldz + i0 + so]));
-            }
-        }
-    };
 
-    acc4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = acc4{A(0), A(0), A(0), A(0)};
-
-    fetch(kbeg);
-    for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            As[so * LD + sk + KS * s] = ra[s];
-            Bs[so * LD + sk + KS * s] = rb[s];
-        }
-        __syncthreads();
-        if (k0 + BK < kend) fetch(k0 + BK);
-        A a[4][4], b[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                a[t][kk] = As[(wm + 16 * t + li) * LD + 4 * g + kk];
-                b[t][kk] = Bs[(wn + 16 * t + li) * LD + 4 * g + kk];
-            }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = M::mma(a[mi][kk], b[ni][kk], acc[mi][ni]);
-    }
+    typename Tile::acc4 acc[4][4];
+    mfma_zero<A>(acc);
+    mfma_tile_product_transposed(
+        t, As, Bs, kbeg, kend, acc,
+        [&](int64_t k, A &a, A &b) {
+            const A gk = gvec[k];
+            int64_t r = idx[k];
+            if (r >= table_rows) r = -1;
+            if (o_ok) a = gk * Op[k * d + o0 + so];
+            if (i_ok && r >= 0) b = A(Elem<T>::to_acc(Z[r * ldz + i0 + so]));
+        },
+        [](A) {});
 
     A *__restrict__ out = ws + (int64_t(blockIdx.z) * 2 + side) * d * d;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const int i = i0 + wn + 16 * ni + li;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int o = o0 + wm + 16 * mi + M::row(lane, reg);
-                if (o < d && i < d) out[int64_t(o) * d + i] = acc[mi][ni][reg];
-            }
-        }
+    mfma_for_each(t, acc, [&](int r, int c, A v) {
+        const int o = o0 + r, i = i0 + c;
+        if (o < d && i < d) out[int64_t(o) * d + i] = v;
+    });
 }
 
 // dW[e] = (sum over the chunks, in chunk order, of ws[c * n + e]) / M, M = stats[1]; M == 0: dW = 0.
