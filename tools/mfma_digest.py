@@ -2,8 +2,11 @@
 """SHA-256 of every output buffer of the dense (MFMA) kernels on fixed non-integer float inputs, as one JSON object.
 
 The integer-data tests of the suite cannot see a changed accumulation order (integer sums are order-free) and the
-fp64-bound tests allow one; this tool can: run it on two builds of the library and compare the files -- any differing
-digest is a changed bit.  It calls only the clane_amd._hip wrappers, so the same file runs against an older checkout.
+fp64-bound tests allow one.  Inside ONE build tests/test_gpu_dense_bits.py sees it: every dense kernel must form a dot
+with the bits project_rows forms, so an order that differs between two kernels, two tiles or two places of a list fails
+there.  An order that changes in every kernel alike passes it, and that is what this tool is for: run it on two builds
+of the library and compare the files -- any differing digest is a changed bit.  It calls only the clane_amd._hip
+wrappers, so the same file runs against an older checkout.
 
 Usage: python tools/mfma_digest.py [--out FILE]
 """
