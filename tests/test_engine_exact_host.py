@@ -1,0 +1,206 @@
+"""The exact engine-level sweeps of tests/engine_exact_cases.py, without a GPU: every case builder's range assertion,
+the single-dropped-edge sensitivity for the sorted P order, every check of tests/test_gpu_engine_exact.py run through
+the CPU test double with the same torch.equal / == comparisons -- which proves the fixtures exact and the expectations
+right before SweepEngine ever drives a HIP kernel against them -- and mutation self-checks: a wrapping double that is
+wrong in one named way must fail the named comparison and no other (a moved table element also moves the snapshot
+distance, which is read off the same table: the two are named together)."""
+import threading
+
+import numpy as np
+import pytest
+import torch
+
+from . import engine_exact_cases as X
+from .exact_cases import BF16, F32, F64
+from .oracle_kernels import OracleKernels
+
+DEV = "cpu"
+
+
+@pytest.fixture(scope="module")
+def k():
+    return OracleKernels()
+
+
+# ---- the fixtures ----------------------------------------------------------------------------------------------------
+def test_split_graph_reaches_the_split_route_and_nothing_else_does():
+    g, s = X.graph(), X.graph("split")
+    assert g.deg.max() <= X.SPLIT_EDGES < s.deg.max() == s.V
+    assert sorted(s.deg[s.deg > 12].tolist()) == [129, 300, s.V, s.V]
+    for r in range(s.V):                                      # sorted, unique rows: what HostCSR promises
+        assert (np.diff(s.sorted_colidx[s.rowptr[r]:s.rowptr[r + 1]]) > 0).all()
+
+
+@pytest.mark.parametrize("case", X.ENGINE_CASES + [(F32, 6), (F32, 100), (F32, 132), (BF16, 64), (F64, 64)], ids=X.case_id)
+def test_engine_case_is_exact_and_notices_every_dropped_edge(case):
+    """Building the case asserts the range condition.  exact_cases.K3Case's sensitivity restated for P in the sorted
+    edge order: for d >= 16 no single edge of the longest row (700 edges, the first 600 tried) may vanish without
+    changing the expected storage-dtype row."""
+    c = X.engine_case(*case)
+    assert c.bound * 8 < X.E.EXACT_LIMIT
+    tried, undetected = c.undetected_single_edge_drops()
+    assert tried == 600
+    if c.d >= 16:
+        assert undetected == 0, (X.case_id(case), undetected)
+
+
+@pytest.mark.parametrize("case", X.SPLIT_CASES, ids=X.case_id)
+def test_split_case_is_exact_and_notices_every_dropped_edge(case):
+    c = X.engine_case(case[0], case[1], "split")
+    assert c.bound * 8 < X.E.EXACT_LIMIT and c.d * (c.bound + 4) * 8 < X.E.EXACT_LIMIT
+    tried, undetected = c.undetected_single_edge_drops()
+    assert (tried, undetected) == (600, 0)
+
+
+def test_sequence_case_stays_within_its_bit_budget():
+    """SequenceCase asserts 2^53 quanta against its bounds sweep by sweep; here, the figures: after three sweeps the
+    largest value needs fewer than 44 bits, the total delta fewer than 49, and the third sweep still moves most rows."""
+    c = X.sequence_case()
+    assert float(c.Z[3].abs().max()) * 2.0 ** 39 < 2.0 ** 44 and c.deltas[2] * 2.0 ** 39 < 2.0 ** 49
+    assert c.deltas[0] > c.deltas[1] > c.deltas[2] > 0 and c.distance != c.deltas[0] + c.deltas[1]
+    moved = (c.Z[3] != c.Z[2]).any(1)
+    sink = X.graph().sink                       # a row that reads only sinks is at its fixed point after one sweep
+    assert int(moved[~sink].sum()) > 400 and not bool(moved[sink].any())
+
+
+def test_load_P_is_the_inverse_of_P_global(k):
+    c = X.engine_case(F32, 128)
+    eng = X.make_engine(k, DEV, c, **X.PLANS["chunks3_class"][0])
+    assert not np.array_equal(eng.local.edge_origin, np.arange(eng.E_loc)) and torch.equal(eng.P_global(), c.P.float())
+
+    def rank_fn(rank, comm):
+        eng = X.make_engine(k, DEV, c, comm=comm, **X.division_settings("halo", True, True))
+        return eng.P_global(), eng.local.edge_origin
+
+    E_all = X.graph().E
+    seen = torch.zeros(E_all)
+    for P, origin in X.run_ranks(3, rank_fn, DEV):
+        full, own = torch.zeros(E_all), torch.zeros(E_all, dtype=torch.bool)
+        full[:P.numel()] = P
+        own[torch.from_numpy(origin)] = True
+        assert torch.equal(full[own], c.P.float()[own]) and float(full[~own].abs().sum()) == 0
+        seen += own
+    assert bool((seen == 1).all())                            # every edge on exactly one rank
+
+
+# ---- the checks on the double ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("run", X.PLAN_RUNS, ids=X.plan_id)
+def test_one_gpu_plans_on_the_double(k, run):
+    X.check_plan(k, DEV, *run)
+
+
+@pytest.mark.parametrize("plan", list(X.SPLIT_PLANS))
+@pytest.mark.parametrize("case", X.SPLIT_CASES, ids=X.case_id)
+def test_split_route_on_the_double(k, case, plan):
+    X.check_split(k, DEV, case, plan)
+
+
+@pytest.mark.parametrize("run", X.DIVISION_RUNS, ids=X.division_id)
+def test_divisions_on_the_double(k, run):
+    X.check_division(k, DEV, run)
+
+
+@pytest.mark.parametrize("plan", list(X.SEQUENCE_PLANS))
+def test_consecutive_sweeps_on_the_double(k, plan):
+    X.check_sequence(k, DEV, plan)
+
+
+@pytest.mark.parametrize("exchange,world,fused", X.SEQUENCE_DIVISIONS)
+def test_consecutive_sweeps_under_a_division_on_the_double(k, exchange, world, fused):
+    X.check_sequence_division(k, DEV, exchange, world, fused)
+
+
+def test_run_ranks_reports_the_rank_that_failed_first():
+    def rank_fn(rank, comm):
+        if rank == 1:
+            raise ValueError("rank 1 is wrong")
+        comm.all_gather_object(rank)
+
+    with pytest.raises(AssertionError, match="rank 1 is wrong") as info:
+        X.run_ranks(3, rank_fn, DEV)
+    assert info.value.args[0][0][0] == 1
+
+
+# ---- mutation self-checks ------------------------------------------------------------------------------------------------
+class Mutant(OracleKernels):
+    """The double, wrong in one way."""
+
+    def __init__(self, what):
+        self.what, self.calls, self.tls = what, 0, threading.local()
+
+    def spmm_update(self, rowptr, colidx, P, nrows, row0, Z_old, X_, gamma, Z_new, d, long_threshold, partials, **kw):
+        super().spmm_update(rowptr, colidx, P, nrows, row0, Z_old, X_, gamma, Z_new, d, long_threshold, partials, **kw)
+        self.tls.Z_old = Z_old
+        if self.what == "partial_left_out" and self.calls == 0:        # one row's |new - old| never reaches the delta
+            deg = np.diff(rowptr[:nrows + 1].numpy())
+            r = int(np.nonzero((deg > 0) & ((deg <= long_threshold) | (long_threshold == 0)))[0][5])
+            partials[0] -= float((Z_new[r, :d].double() - Z_old[row0 + r, :d].double()).abs().sum())
+            self.calls += 1
+
+    def spmm_update_class(self, colidx, P, item_e0, item_len, item_slot, items_per_block, class_rows, slot_ptr, row0,
+                          Z_old, X_, gamma, Z_new, d, slab, partials, **kw):
+        super().spmm_update_class(colidx, P, item_e0, item_len, item_slot, items_per_block, class_rows, slot_ptr, row0,
+                                  Z_old, X_, gamma, Z_new, d, slab, partials, **kw)
+        if self.what == "class_element_moved":                         # by one quantum of the recipe
+            Z_new[int(class_rows[1]), d - 1] += 0.125
+
+    def gather_rows(self, src, idx, d, dst):
+        if self.what == "halo_rows_one_sweep_late":                    # the rows as they were BEFORE this sweep
+            src = self.tls.Z_old
+        super().gather_rows(src, idx, d, dst)
+
+    def l1_distance(self, A, B, d, ws, out, sq_a=None):
+        super().l1_distance(A, B, d, ws, out, sq_a=sq_a)
+        self.calls += 1
+        if self.what == "l1_skips_a_block" and self.calls == 2:
+            out[0] = 0.0
+
+
+ONE_SWEEP_NAMES = ["Z", "Z sinks", "pad columns", "delta", "snapshot distance"]
+
+
+def _plan(kernels, case, plan):
+    settings, route = X.PLANS[plan]
+    return X.run_plan(kernels, DEV, X.engine_case(*case), settings, route, plan)
+
+
+def test_unmutated_wrapper_passes_and_every_comparison_is_made():
+    checks = _plan(Mutant(None), (F32, 128), "chunks3_class")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed == []
+
+
+def test_mutation_a_rows_partial_left_out_of_the_delta():
+    checks = _plan(Mutant("partial_left_out"), (F32, 128), "row_pass_only")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["delta"]
+    (name, got, want, off, _, blocks), = checks.failed
+    assert off < 0 and blocks == [(0, got, want)]                  # the message names the block that is short
+
+
+def test_mutation_one_element_of_a_class_row_moved_by_a_quantum():
+    """The table is wrong, the returned delta (made of the kernels' partials) is not.  The snapshot distance is read
+    off the same table, so it moves by the same quantum: it cannot pass, and is named next to Z."""
+    checks = _plan(Mutant("class_element_moved"), (F32, 128), "class_chunk64")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["Z", "snapshot distance"]
+    name, _, rows = checks.failed[0]
+    g = X.graph()
+    assert len(rows) == 1 and rows[0][1] == int(g.deg[rows[0][0]]) > 32 and rows[0][2] == 0
+    assert abs(checks.failed[1][3]) == 0.125
+
+
+def test_mutation_halo_rows_handed_over_one_sweep_late():
+    """Unfused halo (gather_rows packs the send buffer) fed the rows of the table the sweep READ: every single-sweep
+    comparison still passes (a rank's read-outs cover its own rows), the second consecutive sweep does not."""
+    mutant = Mutant("halo_rows_one_sweep_late")
+    single = X.run_division(mutant, DEV, X.engine_case(F64, 64), "halo", 3, False, False, "late halo, one sweep")
+    assert single.failed == [] and set(single.names) == set(ONE_SWEEP_NAMES)
+    failed = X.run_sequence_division(mutant, DEV, "halo", 3, False, "late halo, sequence").failed_names()
+    assert failed[0] == "Z after sweep 2" and "delta of sweep 2" in failed
+    assert not any(name.endswith("sweep 1") for name in failed)
+    X.run_sequence_division(Mutant(None), DEV, "halo", 3, False, "wrapper alone").assert_none_failed()
+
+
+def test_mutation_l1_distance_skips_a_block():
+    checks = _plan(Mutant("l1_skips_a_block"), (F32, 128), "chunks3_in_order")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["snapshot distance"]
+    sequence = X.run_sequence(Mutant("l1_skips_a_block"), DEV, X.SEQUENCE_PLANS["chunks3_class"], "l1 skips a block")
+    assert sequence.failed_names() == ["snapshot distance after sweep 2"]
