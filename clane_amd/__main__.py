@@ -83,6 +83,18 @@ def embedding(args):
         if not isinstance(node_clu, dict) or ("labels" not in node_clu and "clusters" not in node_clu):
             raise ValueError("node_clustering: the section needs 'labels', the file of id<TAB>class lines, or 'clusters', "
                              "the number of clusters")
+    # optional section (extension): new_vertices: {root: arrivals, max_rounds: 64, weights: true} -- vertices that are not
+    # in V, embedded against the finished graph (induct.py); everything about the files is checked before the graph loads
+    new_vertices = hparams.get("new_vertices") if isinstance(hparams, dict) else None
+    arrivals = None
+    if new_vertices is not None:
+        from . import induct
+        from .graph import read_vertex_ids
+        new_vertices = induct.check_section(new_vertices, int(os.environ.get("WORLD_SIZE", "1")))
+        arrivals_root = Path(new_vertices["root"])
+        if not arrivals_root.is_absolute():
+            arrivals_root = Path(args.data_root) / arrivals_root
+        arrivals = induct.read_arrivals(arrivals_root, read_vertex_ids(Path(args.data_root)), None)
 
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
@@ -90,6 +102,8 @@ def embedding(args):
 
     device = torch.device('cuda') if args.gpu else torch.device('cpu')
     g = Graph(data_root=args.data_root, **hparams["graph"])
+    if arrivals is not None and arrivals[1].shape[1] != g.d:       # the one check that needs the graph: before any sweep
+        raise ValueError(f"new_vertices: content must be [{len(arrivals[0])}, {g.d}], got {tuple(arrivals[1].shape)}")
 
     if world > 1:                                   # unseeded N(0,1) content (no C.npy) must agree across ranks
         import torch.distributed as dist
@@ -234,6 +248,18 @@ def embedding(args):
                     io.write(f"{g.vertex_ids[v]}\t{c}\n")
         say(f"The clustering of {first['clustered']} vertices into {first['clusters']} clusters is stored in "
             f"{out.absolute()}.")
+
+    if arrivals is not None:                        # with the similarity the run ends with: trained weights included
+        from . import induct
+        new_ids, X_new, rowptr, cols = arrivals
+        emb = hparams.get("embedder") or {}
+        res = g.embed_new(similarity_measure, X_new, (rowptr, cols), gamma=emb.get("gamma", 0.76),
+                          tolerence=emb.get("tolerence", 10), max_rounds=new_vertices["max_rounds"],
+                          weights=new_vertices["weights"])
+        report = induct.write_results(args.output_root, new_ids, g.vertex_ids, res, similarity_measure,
+                                      new_vertices["max_rounds"], new_vertices["weights"])
+        say(f"The embeddings of {report['new_vertices']} new vertices ({report['not_converged']} not converged) are "
+            f"stored in {args.output_root.joinpath('Z_new.npy').absolute()}.")
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

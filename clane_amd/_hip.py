@@ -114,6 +114,11 @@ for _s in ("f32", "f64", "bf16"):   # node clustering (csrc/kmeans.h)
     SIGNATURES[f"clane_kmeans_update_{_s}"] = (
         C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p])
 SIGNATURES["clane_kmeans_update_ws_len"] = (_i64, [_i64, _i32, _i32, _i32])
+for _s in ("f32", "f64", "bf16"):   # new vertices against the finished table (csrc/new_rows.h)
+    _g = C.c_double if _s == "f64" else C.c_float
+    SIGNATURES[f"clane_embed_rows_{_s}"] = (
+        C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _g, _i32, _i32, _i32, _p, _i64,
+                  _p, _p, _p, _p])
 
 
 def probe_padded_classes(C_: int) -> int:
@@ -485,6 +490,13 @@ class KernelBackend(abc.ABC):
         pre-marshal it (HipKernels does)."""
         fn = getattr(self, method)
         return lambda: fn(*args, **kwargs)
+
+    # new vertices (induct.py): optional in the same way -- NewVertexEmbedder is the only caller
+    def embed_rows(self, rowptr, colidx, X_new, Z, table_rows: int, d: int, mode: int, sums2, sq, S, gamma: float,
+                   tolerence: int, max_rounds: int, Z_out, rounds, delta, P_out=None, flags: int = 0):
+        """The per-row fixed point of build_P + update on the frozen table Z for the rows of the CSR (rowptr, colidx =
+        table rows): Z_out, rounds, delta and, where wanted, the soft-max weights P_out (csrc/new_rows.h)."""
+        raise NotImplementedError(f"{type(self).__name__} has no embed_rows")
 
 
 class HipKernels(KernelBackend):
@@ -1045,6 +1057,33 @@ class HipKernels(KernelBackend):
         self._check(self._fn("clane_pair_cosine", A.dtype)(
             ap, lda, bp, ldb, A.shape[0], d, _vec(out, acc_dtype(A.dtype), "out"), _vec(ws, torch.float64, "ws"),
             self._stream(A)), "clane_pair_cosine")
+
+    # -- new vertices ---------------------------------------------------------------------
+    def embed_rows(self, rowptr, colidx, X_new, Z, table_rows: int, d: int, mode: int, sums2, sq, S, gamma: float,
+                   tolerence: int, max_rounds: int, Z_out, rounds, delta, P_out=None, flags: int = 0):
+        xp, ldx = _mat(X_new, "X_new")
+        zp, ldz = _mat(Z, "Z")
+        op, ldo = _mat(Z_out, "Z_out")
+        acc, m = acc_dtype(Z.dtype), X_new.shape[0]
+        if X_new.dtype != Z.dtype or Z_out.dtype != Z.dtype:
+            raise ValueError("embed_rows: X_new, Z and Z_out must share a dtype")
+        if Z.shape[0] < table_rows or min(Z.shape[1], X_new.shape[1], Z_out.shape[1]) < d or Z_out.shape[0] < m:
+            raise ValueError(f"embed_rows: Z needs {table_rows} rows, X_new / Z / Z_out {d} columns, Z_out {m} rows")
+        if rowptr.numel() < m + 1 or rounds.numel() < m or delta.numel() < m:
+            raise ValueError("embed_rows: rowptr needs m + 1 entries, rounds and delta one per new row")
+        if sq is not None and sq.numel() < table_rows:
+            raise ValueError("embed_rows: sq needs one entry per table row")
+        sp, lds = (None, 0)
+        if S is not None:
+            sp, lds = _mat(S, "S")
+            if S.dtype != acc or S.shape[0] < table_rows or S.shape[1] < d:
+                raise ValueError(f"embed_rows: S must be {acc} with at least {table_rows} rows of {d} columns")
+        self._invoke(self._fn("clane_embed_rows", Z.dtype), "clane_embed_rows",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), m, xp, ldx, zp,
+                     table_rows, ldz, d, mode, _ptr(sums2), None if sq is None else _vec(sq, acc, "sq"), sp, lds,
+                     float(gamma), int(tolerence), int(max_rounds), int(flags), op, ldo,
+                     _vec(rounds, torch.int32, "rounds"), _vec(delta, acc, "delta"),
+                     None if P_out is None else _vec(P_out, acc, "P_out"), self._stream(Z))
 
 
 _kernels: Optional[HipKernels] = None

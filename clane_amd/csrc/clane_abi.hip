@@ -15,6 +15,7 @@
 #include "kmeans.h"
 #include "label_probe.h"
 #include "multilabel_probe.h"
+#include "new_rows.h"
 #include "link_eval.h"
 #include "link_rank.h"
 #include "pair_train.h"
@@ -732,6 +733,68 @@ int pair_score(const T *S, int64_t lds, const T *N, int64_t ldn, int64_t table_r
     return check_launch("pair_score");
 }
 
+// ---- new vertices against the finished table (new_rows.h) ------------------------------------------------------------
+template <typename T, typename GT>
+int embed_rows(const int64_t *rowptr, const int32_t *colidx, int64_t m, const T *X_new, int64_t ldx, const T *Z,
+               int64_t table_rows, int64_t ldz, int32_t d, int32_t mode, const double *sums2,
+               const typename Elem<T>::acc_t *sq, const typename Elem<T>::acc_t *S, int64_t lds, GT gamma,
+               int32_t tolerence, int32_t max_rounds, int32_t flags, T *Z_out, int64_t ldo, int32_t *rounds,
+               typename Elem<T>::acc_t *delta, typename Elem<T>::acc_t *P_out, void *stream) {
+    using A = typename Elem<T>::acc_t;
+    REQUIRE(m >= 0, "embed_rows: m = %lld is negative", (long long)m);
+    REQUIRE(table_rows >= 0, "embed_rows: table_rows = %lld is negative", (long long)table_rows);
+    REQUIRE(d >= 1, "embed_rows: d = %d must be at least 1", d);
+    REQUIRE(ldx >= d && ldz >= d && ldo >= d, "embed_rows: ldx = %lld, ldz = %lld and ldo = %lld must be at least d = %d",
+            (long long)ldx, (long long)ldz, (long long)ldo, d);
+    REQUIRE(score_mode_ok(mode), "embed_rows: unknown mode %d", mode);
+    REQUIRE(S == nullptr || mode == CLANE_SCORE_RAW_DOT, "embed_rows: S (the projected table) goes with mode RAW_DOT only");
+    REQUIRE(S != nullptr || mode != CLANE_SCORE_RAW_DOT, "embed_rows: mode RAW_DOT needs S (the projected table)");
+    REQUIRE(S == nullptr || lds >= d, "embed_rows: lds = %lld must be at least d = %d", (long long)lds, d);
+    REQUIRE(mode != CLANE_SCORE_REFERENCE || sums2, "embed_rows: mode REFERENCE needs sums2");
+    REQUIRE(mode != CLANE_SCORE_PER_EDGE || sq, "embed_rows: mode PER_EDGE needs sq");
+    REQUIRE(tolerence >= 1, "embed_rows: tolerence = %d must be at least 1", tolerence);
+    REQUIRE(max_rounds >= 1, "embed_rows: max_rounds = %d must be at least 1", max_rounds);
+    REQUIRE(flags == 0, "embed_rows: unknown flags %d", flags);
+    REQUIRE(Z_out && rounds && delta, "embed_rows: null output (Z_out, rounds, delta)");
+    if (m == 0) return CLANE_OK;
+    REQUIRE(rowptr && X_new, "embed_rows: null rowptr / X_new");
+    REQUIRE(table_rows == 0 || (colidx && Z), "embed_rows: null colidx / Z");
+    constexpr int KV = Elem<T>::kVec;
+    Layout L = pick_layout<T>(d, {X_new, Z, Z_out}, {ldx, ldz, ldo});
+    if (S != nullptr && L.vec && ((reinterpret_cast<uintptr_t>(S) % (sizeof(A) * KV)) != 0 || lds % KV != 0)) {
+        L.vec = false;                       // score rows are read as packs of KV accumulate-type elements
+        L.lpr = d <= 4 ? 4 : d <= 16 ? 16 : 64;
+    }
+    const int width = L.lpr * (L.vec ? KV : 1);
+    const bool wide = d > width;
+    const int dpad = int(ceil_div(d, width)) * width;
+    REQUIRE(!wide || int64_t(dpad) * 2 * int64_t(sizeof(A)) <= kEmbedWideLdsPerWave,
+            "embed_rows: d = %d is more than this layout keeps per row (%d)", d,
+            int(kEmbedWideLdsPerWave / (2 * sizeof(A)) / width * width));
+    const int rpb = rows_per_block(m);
+    const unsigned grid = unsigned(row_grid(m));
+    const A g = A(gamma);
+    auto launch = [&]<int VEC, int LPR, bool PAIR, bool WIDE>() {
+        constexpr int U = VEC > 1 ? 8 : 4;
+        const size_t lds_bytes = WIDE ? size_t(kWavesPerBlock) * 2 * dpad * sizeof(A) : 0;
+        embed_rows_kernel<T, VEC, LPR, U, PAIR, WIDE><<<grid, kBlock, lds_bytes, (hipStream_t)stream>>>(
+            rowptr, colidx, m, X_new, ldx, Z, ldz, d, mode, sums2, sq, S, lds, g, tolerence, max_rounds, Z_out, ldo,
+            rounds, delta, P_out, rpb, dpad);
+    };
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
+        if constexpr (LPR == kWave) {
+            if (wide) {
+                if (S) launch.template operator()<VEC, LPR, true, true>();
+                else launch.template operator()<VEC, LPR, false, true>();
+                return;
+            }
+        }
+        if (S) launch.template operator()<VEC, LPR, true, false>();
+        else launch.template operator()<VEC, LPR, false, false>();
+    });
+    return check_launch("embed_rows");
+}
+
 // ---- node classification probe (label_probe.h) ----------------------------------------------------------------------
 inline int64_t probe_row_tiles(int64_t n) { return ceil_div(n > 0 ? n : 1, int64_t(kProjBM)); }
 inline int64_t probe_grad_chunks(int64_t n) { return ceil_div(n > 0 ? n : 1, int64_t(kGradChunk)); }
@@ -1246,6 +1309,22 @@ int clane_rank_merge_f64(const double *cand_score, const int32_t *cand_id, int64
                          double *out_score, int32_t *out_id, void *stream) {
     return rank_merge<double>(cand_score, cand_id, Q, n_slabs, k, out_score, out_id, stream);
 }
+
+#define CLANE_EMBED_WRAPPERS(SUF, CT, T, AT, GT)                                                                        \
+    int clane_embed_rows_##SUF(const int64_t *rowptr, const int32_t *colidx, int64_t m, const CT *X_new, int64_t ldx,   \
+                               const CT *Z, int64_t table_rows, int64_t ldz, int32_t d, int32_t mode,                   \
+                               const double *sums2, const AT *sq, const AT *S, int64_t lds, GT gamma,                   \
+                               int32_t tolerence, int32_t max_rounds, int32_t flags, CT *Z_out, int64_t ldo,            \
+                               int32_t *rounds, AT *delta, AT *P_out, void *stream) {                                   \
+        return embed_rows<T, GT>(rowptr, colidx, m, reinterpret_cast<const T *>(X_new), ldx,                            \
+                                 reinterpret_cast<const T *>(Z), table_rows, ldz, d, mode, sums2, sq, S, lds, gamma,    \
+                                 tolerence, max_rounds, flags, reinterpret_cast<T *>(Z_out), ldo, rounds, delta, P_out, \
+                                 stream);                                                                               \
+    }
+CLANE_EMBED_WRAPPERS(f32, float, float, float, float)
+CLANE_EMBED_WRAPPERS(f64, double, double, double, double)
+CLANE_EMBED_WRAPPERS(bf16, uint16_t, bf16_t, float, float)
+#undef CLANE_EMBED_WRAPPERS
 
 #define CLANE_PROBE_WRAPPERS(SUF, CT, T, AT)                                                                           \
     int clane_probe_forward_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \

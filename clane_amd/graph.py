@@ -509,6 +509,36 @@ class Graph(torch.utils.data.Dataset):
                 f"kernel to score all pairs with")
         return LinkRanker(eng, similarity).evaluate(src, dst, hits, filter_existing).as_dict()
 
+    def embed_new(self, similarity, X_new, neighbours, gamma: float = 0.76, tolerence: int = 10, max_rounds: int = 64,
+                  weights: bool = False):
+        """Embeddings of vertices that are NOT in the graph, against the CURRENT embeddings, which do not move
+        (extension, induct.py): vertex i has content ``X_new[i]`` and out-edges to the existing vertices
+        ``neighbours[i]`` -- a sequence of per-vertex collections of vertex indices, or a tuple ``(rowptr, colidx)`` of
+        two arrays.  The reference's loop restricted to such a row is the fixed point ``z <- x + gamma * sum_v
+        softmax_v(score(z, z_v)) z_v`` on frozen ``Z``, iterated per row with the reference's ``Tolerence`` and at most
+        ``max_rounds`` rounds.  Returns ``induct.NewRows`` on the host (``Z`` in ``X``'s dtype, ``rounds``, ``delta``,
+        ``converged``, the coalesced ``rowptr`` / ``cols`` and with ``weights`` the soft-max weights ``P``).  A repeated
+        neighbour counts once; an index outside ``[0, V)`` is a ValueError, so new vertices cannot link to each other.
+        Similarities and engines as ``predict_links``."""
+        from .induct import SUPPORTED, NewVertexEmbedder, normalize_neighbours
+        from .similarity import AsymmertricSimilarity, CosineSimilarity
+        X_new = torch.as_tensor(X_new)
+        if X_new.dim() != 2 or X_new.shape[1] != self.X.shape[1]:
+            raise ValueError(f"embed_new: X_new must be [m, {self.X.shape[1]}], got {tuple(X_new.shape)}")
+        rowptr, cols = normalize_neighbours(neighbours, int(X_new.shape[0]))
+        if isinstance(similarity, CosineSimilarity):
+            eng = self.engine(cosine_mode=similarity.mode)
+        elif isinstance(similarity, AsymmertricSimilarity):
+            eng = self.engine()
+        else:
+            raise NotImplementedError(
+                f"embed_new scores with {SUPPORTED}; a plug-in similarity ({type(similarity).__name__}) has no kernel "
+                f"to iterate a row with")
+        res = NewVertexEmbedder(eng, similarity).embed(X_new.to(self.X.dtype), rowptr, cols, gamma, tolerence, max_rounds,
+                                                       weights).cpu()
+        res.Z = res.Z.to(self.X.dtype).contiguous()
+        return res
+
     def evaluate_labels(self, labels, ratios=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), runs: int = 10, seed: int = 0,
                         l2: float = 1.0, table: str = "Z", multilabel: bool = False, predict: str = "top_k") -> dict:
         """The reference README's node-classification table for the CURRENT embeddings (extension): a soft-max regression

@@ -60,7 +60,9 @@ extern "C" {
                              *    batched k-means on rows of the table, the arg-min fused into the distances' contraction)
                              *    + clane_probe_forward_ovr_* (multi-label node classification: F stacked one-vs-rest
                              *    regressions, sigmoid loss / gradient and the top-k label masks fused into the logits'
-                             *    contraction; workspaces and clane_probe_grad_* as for the soft-max probe) */
+                             *    contraction; workspaces and clane_probe_grad_* as for the soft-max probe)
+                             *    + clane_embed_rows_* (new vertices embedded against the finished table: the per-row fixed
+                             *    point of build_P + update on frozen Z, one launch, every row stopping on its own) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -654,6 +656,47 @@ int clane_kmeans_update_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, i
                              const int64_t *seg, int64_t n, int32_t R, int32_t K, const float *centres_old, float *ws,
                              float *centres_new, float *csq_new, void *stream);
 int64_t clane_kmeans_update_ws_len(int64_t n, int32_t R, int32_t K, int32_t d);
+
+/* ---- new vertices against a finished table (csrc/new_rows.h) ------------------------------------------------------------
+ * A vertex that was not in V, with content x and out-edges to EXISTING vertices only: nothing reads it, so Graph.build_P
+ * (graph.py:118-128) followed by the update of propagate (embedder.py:84-92), restricted to that row on a table that is
+ * held fixed, is the per-row fixed point  z <- x + gamma * sum_v softmax_v(score(z, z_v)) z_v,  v in nbrs, z^0 = x.
+ * One launch embeds m such rows; each iterates and stops on its own.
+ *   rowptr (int64 [m + 1]) / colidx (int32): the new rows' neighbours as TABLE ROWS of Z (not checked here:
+ *     clane_check_csr); a repeated neighbour counts as often as it is listed.
+ *   X_new [m, ldx], Z [table_rows, ldz], Z_out [m, ldo] in the table type; only columns [0, d) are read, Z_out's columns
+ *     [d, ldo) are written as zeros.
+ *   Score, with z the iterate in the accumulate type:
+ *     S == NULL, mode REFERENCE: z . z_v / sqrt(sums2[0] sums2[1]);  PER_EDGE: z . z_v / (|z| sqrt(sq[v])), |z| recomputed
+ *       from the iterate every round.  sums2 / sq are the EXISTING graph's (clane_degree_weighted_sums_*,
+ *       clane_row_sqnorm_*): the table is frozen, the new edges are NOT counted into the global denominator.
+ *     S != NULL (accumulate type, [table_rows, lds]), mode RAW_DOT: z . S_v -- the bilinear (Phi_src z) . (Phi_dst z_v)
+ *       with S = Z M^T, M = Phi_src.weight^T Phi_dst.weight (the first d columns of clane_project_rows_* with M stacked
+ *       on zeros).  Values always come from Z.
+ *   A round is one pass over the row's neighbours with an online soft-max.  Stop rule, the reference's Tolerence per row:
+ *     a round whose delta = sum |z_new - z| is a new minimum of the row resets the counter to `tolerence`, any other round
+ *     decrements it; the row ends at counter 0, after max_rounds rounds, or at delta == 0.
+ *   rounds (int32 [m]): rounds run, 0 for a row without neighbours, which returns x (embedder.py:88-89);
+ *   delta ([m], accumulate type): the last round's; P_out ([rowptr[m]], accumulate type, or NULL): the soft-max weights
+ *   that produced the returned z, in colidx order.  z is rounded to the table type once, on the store.
+ *   flags: 0.  d beyond 64 packs per row (vector layout) is kept in LDS: at most 2048 (f32, bf16) / 1024 (f64) columns.
+ * No allocation, no synchronisation, no atomics on memory; a row's results do not depend on where it sits in the batch
+ * or on what else is in it, and two calls give the same bits. */
+int clane_embed_rows_f32(const int64_t *rowptr, const int32_t *colidx, int64_t m, const float *X_new, int64_t ldx,
+                         const float *Z, int64_t table_rows, int64_t ldz, int32_t d, int32_t mode, const double *sums2,
+                         const float *sq, const float *S, int64_t lds, float gamma, int32_t tolerence,
+                         int32_t max_rounds, int32_t flags, float *Z_out, int64_t ldo, int32_t *rounds, float *delta,
+                         float *P_out, void *stream);
+int clane_embed_rows_f64(const int64_t *rowptr, const int32_t *colidx, int64_t m, const double *X_new, int64_t ldx,
+                         const double *Z, int64_t table_rows, int64_t ldz, int32_t d, int32_t mode, const double *sums2,
+                         const double *sq, const double *S, int64_t lds, double gamma, int32_t tolerence,
+                         int32_t max_rounds, int32_t flags, double *Z_out, int64_t ldo, int32_t *rounds, double *delta,
+                         double *P_out, void *stream);
+int clane_embed_rows_bf16(const int64_t *rowptr, const int32_t *colidx, int64_t m, const uint16_t *X_new, int64_t ldx,
+                          const uint16_t *Z, int64_t table_rows, int64_t ldz, int32_t d, int32_t mode,
+                          const double *sums2, const float *sq, const float *S, int64_t lds, float gamma,
+                          int32_t tolerence, int32_t max_rounds, int32_t flags, uint16_t *Z_out, int64_t ldo,
+                          int32_t *rounds, float *delta, float *P_out, void *stream);
 
 #ifdef __cplusplus
 }
