@@ -83,6 +83,14 @@ def embedding(args):
         if not isinstance(node_clu, dict) or ("labels" not in node_clu and "clusters" not in node_clu):
             raise ValueError("node_clustering: the section needs 'labels', the file of id<TAB>class lines, or 'clusters', "
                              "the number of clusters")
+    # optional section (extension): content_reduction: {dim: 128, center: true, whiten: false, load: pca.npz} -- the
+    # content's principal components instead of the content (reduce.py); checked before the graph loads
+    reduction = hparams.get("content_reduction") if isinstance(hparams, dict) else None
+    reduction_file = None
+    if reduction is not None:
+        from . import reduce
+        reduction = reduce.check_section(reduction, int(os.environ.get("WORLD_SIZE", "1")))
+        reduction_file = reduce.resolve_load(reduction, Path(args.data_root))
     # optional section (extension): new_vertices: {root: arrivals, max_rounds: 64, weights: true} -- vertices that are not
     # in V, embedded against the finished graph (induct.py); everything about the files is checked before the graph loads
     new_vertices = hparams.get("new_vertices") if isinstance(hparams, dict) else None
@@ -102,6 +110,26 @@ def embedding(args):
 
     device = torch.device('cuda') if args.gpu else torch.device('cpu')
     g = Graph(data_root=args.data_root, **hparams["graph"])
+    if reduction is not None:                       # before the banner: its statistics are the reduced content's
+        from .reduce import ContentPCA
+        original_width = int(g.X.shape[1])
+        if arrivals is not None and arrivals[1].shape[1] != original_width:
+            raise ValueError(f"new_vertices: with content_reduction the arrivals' content must have the graph's ORIGINAL "
+                             f"width {original_width} (it is reduced to {reduction['dim'] or 'the loaded width'} by the "
+                             f"graph's transform), got {tuple(arrivals[1].shape)}")
+        if reduction_file is not None:
+            loaded = ContentPCA.load(reduction_file)
+            if reduction["dim"] is not None and reduction["dim"] != loaded.dim:
+                raise ValueError(f"content_reduction: dim = {reduction['dim']} but {str(reduction_file)!r} reduces to "
+                                 f"{loaded.dim} columns")
+            if loaded.components_.shape[1] != original_width:
+                raise ValueError(f"content_reduction: {str(reduction_file)!r} was fitted on {loaded.components_.shape[1]} "
+                                 f"columns, the content has {original_width}")
+            g.reduce_content(loaded.dim, transform=loaded)
+        else:
+            g.reduce_content(reduction["dim"], center=reduction["center"], whiten=reduction["whiten"])
+        if arrivals is not None:                    # the graph's mean and components, never a re-fit
+            arrivals = (arrivals[0], g.content_transform.transform(arrivals[1].to(g.X.dtype).contiguous()), *arrivals[2:])
     if arrivals is not None and arrivals[1].shape[1] != g.d:       # the one check that needs the graph: before any sweep
         raise ValueError(f"new_vertices: content must be [{len(arrivals[0])}, {g.d}], got {tuple(arrivals[1].shape)}")
 
@@ -114,7 +142,11 @@ def embedding(args):
     say("Graph Loaded.")
     say(f" - {len(g)} vertices")
     say(f" - {len(g.E)} edges")
-    say(" - Content Embeddings:")
+    if reduction is not None:
+        say(f" - Content Embeddings (reduced from {original_width} columns; "
+            f"{g.content_transform.explained_variance_ratio_.sum():.3f} of the variance kept):")
+    else:
+        say(" - Content Embeddings:")
     say(f"     - dim : {g.d:3d}")
     say(f"     - mean: {g.X.mean():5.2f}")
     say(f"     - std : {g.X.std():5.2f}")
@@ -171,6 +203,15 @@ def embedding(args):
     np.save(args.output_root.joinpath('Z.npy'), _to_numpy(final_Z))
 
     say(f"The embeddings are stored in {args.output_root.joinpath('Z.npy').absolute()}.")
+
+    if reduction is not None:
+        import json
+        g.content_transform.save(args.output_root.joinpath('content_projection.npz'))
+        with open(args.output_root.joinpath('content_reduction.json'), "w") as io:
+            json.dump(g.content_transform.report(original_width), io, indent=1)
+            io.write("\n")
+        say(f"The content projection ({original_width} -> {g.d} columns) is stored in "
+            f"{args.output_root.joinpath('content_projection.npz').absolute()}.")
 
     if predict_k is not None:
         from .links import read_link_sources, write_links_tsv

@@ -120,6 +120,14 @@ for _s in ("f32", "f64", "bf16"):   # new vertices against the finished table (c
         C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _g, _i32, _i32, _i32, _p, _i64,
                   _p, _p, _p, _p])
 
+PCA_ACCUMULATE = 1                  # CLANE_PCA_ACCUMULATE
+for _s in ("f32", "f64", "bf16"):   # content reduction (csrc/content_pca.h)
+    SIGNATURES[f"clane_column_sums_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _i32, _p, _p, _p])
+    SIGNATURES[f"clane_gram_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _p])
+    SIGNATURES[f"clane_project_affine_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _i32, _p, _i64, _p])
+SIGNATURES["clane_column_sums_ws_len"] = (_i64, [_i64, _i32])
+SIGNATURES["clane_gram_ws_len"] = (_i64, [_i64, _i32])
+
 
 def probe_padded_classes(C_: int) -> int:
     """Cp: the columns a fit takes in the stacked weights -- C rounded up to a power of two."""
@@ -484,6 +492,28 @@ class KernelBackend(abc.ABC):
         """centres_new[r, j] = the mean of the table rows order[seg[r K + j] : seg[r K + j + 1]] (the old centre where
         the segment is empty), csq_new its squared norm.  order holds restart r's n rows at [r n, (r + 1) n)."""
         raise NotImplementedError(f"{type(self).__name__} has no kmeans_update")
+
+    # content reduction (reduce.py): optional in the same way -- ContentPCA is the only caller.  rows are TABLE ROWS
+    # (int32; an entry outside the table is an absent row); mu, W, G and the Gram's workspace in the accumulate dtype.
+    def column_sums_ws_len(self, n: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no column_sums_ws_len")
+
+    def column_sums(self, Z, d: int, rows, ws, sums, accumulate: bool = False):
+        """sums [d] (float64) = the column sums of Z[rows, :d], rows in chunks of 2048, the chunks in order; with
+        ``accumulate`` on top of what sums holds."""
+        raise NotImplementedError(f"{type(self).__name__} has no column_sums")
+
+    def gram_ws_len(self, n: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no gram_ws_len")
+
+    def gram(self, Z, d: int, rows, mu, ws, G, accumulate: bool = False):
+        """G [d, d] = sum_i (z_i - mu)(z_i - mu)^T over Z[rows, :d] (mu None: no centring), bitwise symmetric; with
+        ``accumulate`` on top of what G holds."""
+        raise NotImplementedError(f"{type(self).__name__} has no gram")
+
+    def project_affine(self, Z, d: int, rows, mu, W, Y):
+        """Y[i, :m] = W (Z[rows[i], :d] - mu), W [m, d]; Y in Z's dtype, rounded once."""
+        raise NotImplementedError(f"{type(self).__name__} has no project_affine")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -1049,6 +1079,47 @@ class HipKernels(KernelBackend):
                      zp, Z.shape[0], d, ldz, _vec(order, torch.int32, "order"), _vec(seg, torch.int64, "seg"), n, R, K,
                      _vec(centres_old, acc, "centres_old"), _vec(ws, acc, "ws"), _vec(centres_new, acc, "centres_new"),
                      _vec(csq_new, acc, "csq_new"), self._stream(Z))
+
+    # -- content reduction -----------------------------------------------------------------
+    def column_sums_ws_len(self, n: int, d: int) -> int:
+        return int(self.lib.clane_column_sums_ws_len(n, d))
+
+    def gram_ws_len(self, n: int, d: int) -> int:
+        return int(self.lib.clane_gram_ws_len(n, d))
+
+    def column_sums(self, Z, d: int, rows, ws, sums, accumulate: bool = False):
+        zp, ldz = _mat(Z, "Z")
+        n = rows.numel()
+        if sums.numel() != d or ws.numel() < self.column_sums_ws_len(n, d):
+            raise ValueError("column_sums: sums needs d doubles, ws column_sums_ws_len(n, d)")
+        self._invoke(self._fn("clane_column_sums", Z.dtype), "clane_column_sums",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, PCA_ACCUMULATE if accumulate else 0,
+                     _vec(ws, torch.float64, "ws"), _vec(sums, torch.float64, "sums"), self._stream(Z))
+
+    def gram(self, Z, d: int, rows, mu, ws, G, accumulate: bool = False):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        if tuple(G.shape) != (d, d) or ws.numel() < self.gram_ws_len(n, d) or (mu is not None and mu.numel() != d):
+            raise ValueError(f"gram: G must be [{d}, {d}], mu [{d}] or None, ws gram_ws_len(n, d) elements")
+        self._invoke(self._fn("clane_gram", Z.dtype), "clane_gram",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n,
+                     None if mu is None else _vec(mu, acc, "mu"), PCA_ACCUMULATE if accumulate else 0,
+                     _vec(ws, acc, "ws"), _vec(G, acc, "G"), self._stream(Z))
+
+    def project_affine(self, Z, d: int, rows, mu, W, Y):
+        zp, ldz = _mat(Z, "Z")
+        yp, ldy = _mat(Y, "Y")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        if W.dim() != 2 or W.shape[1] != d or W.shape[0] < 1 or (mu is not None and mu.numel() != d):
+            raise ValueError(f"project_affine: W must be [m, d = {d}] and mu [{d}] or None, got {tuple(W.shape)}")
+        m = int(W.shape[0])
+        if Y.dtype != Z.dtype or Y.shape[0] < n or Y.shape[1] < m:
+            raise ValueError(f"project_affine: Y must be {Z.dtype} with at least {n} rows of {m} columns")
+        self._invoke(self._fn("clane_project_affine", Z.dtype), "clane_project_affine",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n,
+                     None if mu is None else _vec(mu, acc, "mu"), _vec(W, acc, "W"), m, yp, ldy, self._stream(Z))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "build_p.h"
+#include "content_pca.h"
 #include "edge_score.h"
 #include "device_utils.h"
 #include "kmeans.h"
@@ -944,6 +945,73 @@ int kmeans_update(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const 
     return check_launch("kmeans_update");
 }
 
+// ---- content reduction (content_pca.h) --------------------------------------------------------------------------------
+inline int64_t pca_chunks(int64_t n) { return n > 0 ? ceil_div(n, int64_t(kGradChunk)) : 0; }
+
+template <typename T>
+int column_sums(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, int32_t flags,
+                double *ws, double *sums, void *stream) {
+    static_assert(kPcaAccumulate == CLANE_PCA_ACCUMULATE, "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d,
+            "column_sums: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    REQUIRE((flags & ~CLANE_PCA_ACCUMULATE) == 0, "column_sums: unknown flags %d", flags);
+    REQUIRE(ws && sums, "column_sums: null workspace/output");
+    REQUIRE(n == 0 || (Z && rows), "column_sums: null pointer");
+    const int64_t n_chunks = pca_chunks(n);
+    REQUIRE(n_chunks <= 65535, "column_sums: %lld rows is too many for one launch", (long long)n);
+    constexpr int KV = Elem<T>::kVec;
+    const unsigned strips = unsigned(ceil_div(int64_t(d), int64_t(kSumColLanes * KV)));
+    if (n_chunks > 0) {
+        if (aligned16(Z) && ldz % KV == 0)
+            column_sums_kernel<T, KV, true><<<dim3(strips, unsigned(n_chunks)), kBlock, 0, (hipStream_t)stream>>>(
+                Z, table_rows, d, ldz, rows, n, ws);
+        else
+            column_sums_kernel<T, KV, false><<<dim3(strips, unsigned(n_chunks)), kBlock, 0, (hipStream_t)stream>>>(
+                Z, table_rows, d, ldz, rows, n, ws);
+    }
+    column_sums_reduce_kernel<<<unsigned(ceil_div(int64_t(d), int64_t(kBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        ws, n_chunks, d, flags & CLANE_PCA_ACCUMULATE, sums);
+    return check_launch("column_sums");
+}
+
+template <typename T, typename A>
+int gram(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *mu,
+         int32_t flags, A *ws, A *G, void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d,
+            "gram: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d, (long long)ldz);
+    REQUIRE((flags & ~CLANE_PCA_ACCUMULATE) == 0, "gram: unknown flags %d", flags);
+    REQUIRE(ws && G, "gram: null workspace/output");
+    REQUIRE(n == 0 || (Z && rows), "gram: null pointer");
+    const int64_t n_chunks = pca_chunks(n);
+    REQUIRE(n_chunks <= 65535, "gram: %lld rows is too many for one launch", (long long)n);
+    const int64_t nt = ceil_div(int64_t(d), int64_t(kProjBN));
+    const int64_t len = int64_t(d) * d;
+    if (n_chunks > 0)
+        gram_kernel<T, A><<<dim3(unsigned(nt * (nt + 1) / 2), unsigned(n_chunks)), kBlock, 0, (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, n, mu, ws, int(nt));
+    gram_reduce_kernel<A><<<unsigned(ceil_div(len, int64_t(kBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        ws, n_chunks, d, flags & CLANE_PCA_ACCUMULATE, G);
+    return check_launch("gram");
+}
+
+template <typename T, typename A>
+int project_affine(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *mu,
+                   const A *W, int32_t m, T *Y, int64_t ldy, void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d && m >= 1 && ldy >= m,
+            "project_affine: bad shape rows=%lld n=%lld d=%d ldz=%lld m=%d ldy=%lld", (long long)table_rows,
+            (long long)n, d, (long long)ldz, m, (long long)ldy);
+    if (n == 0) return CLANE_OK;
+    REQUIRE(Z && rows && W && Y, "project_affine: null pointer");
+    const int n_tiles = int(ceil_div(int64_t(m), int64_t(kProjBN)));
+    const int64_t blocks = ceil_div(n, int64_t(kProjBM)) * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "project_affine: %lld rows x %d columns is too many for one launch", (long long)n, m);
+    project_affine_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(Z, table_rows, d, ldz, rows, n, mu,
+                                                                                       W, m, Y, ldy, n_tiles);
+    return check_launch("project_affine");
+}
+
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1377,6 +1445,30 @@ CLANE_KMEANS_WRAPPERS(bf16, uint16_t, bf16_t, float)
 int64_t clane_kmeans_update_ws_len(int64_t n, int32_t R, int32_t K, int32_t d) {
     (void)K;                                     /* two chunk sums per window of the sorted list, whatever K */
     return 2 * kmeans_windows(n, R) * int64_t(d > 0 ? d : 0);
+}
+
+#define CLANE_PCA_WRAPPERS(SUF, CT, T, AT)                                                                             \
+    int clane_column_sums_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,          \
+                                int64_t n, int32_t flags, double *ws, double *sums, void *stream) {                    \
+        return column_sums<T>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, flags, ws, sums, stream);   \
+    }                                                                                                                  \
+    int clane_gram_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,      \
+                         const AT *mu, int32_t flags, AT *ws, AT *G, void *stream) {                                   \
+        return gram<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, mu, flags, ws, G, stream);     \
+    }                                                                                                                  \
+    int clane_project_affine_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,       \
+                                   int64_t n, const AT *mu, const AT *W, int32_t m, CT *Y, int64_t ldy,                \
+                                   void *stream) {                                                                     \
+        return project_affine<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, mu, W, m,            \
+                                     reinterpret_cast<T *>(Y), ldy, stream);                                           \
+    }
+CLANE_PCA_WRAPPERS(f32, float, float, float)
+CLANE_PCA_WRAPPERS(f64, double, double, double)
+CLANE_PCA_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_PCA_WRAPPERS
+int64_t clane_column_sums_ws_len(int64_t n, int32_t d) { return (pca_chunks(n) > 0 ? pca_chunks(n) : 1) * int64_t(d > 0 ? d : 0); }
+int64_t clane_gram_ws_len(int64_t n, int32_t d) {
+    return (pca_chunks(n) > 0 ? pca_chunks(n) : 1) * int64_t(d > 0 ? d : 0) * int64_t(d > 0 ? d : 0);
 }
 
 }  // extern "C"

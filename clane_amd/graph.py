@@ -627,6 +627,34 @@ class Graph(torch.utils.data.Dataset):
             out["assignments"] = km.last_fit.assign[:, out["best_restart"]].tolist()
         return out
 
+    def reduce_content(self, dim: int, center: bool = True, whiten: bool = False, block_rows=None, transform=None):
+        """Replace the content embeddings ``X`` (and ``d``) by their ``dim`` principal components (extension, reduce.py:
+        column sums, centred Gram and projection on the GPU, the ``d x d`` eigen-problem on the host) and keep the
+        fitted ``ContentPCA`` as ``self.content_transform`` -- new vertices' content has to go through the same one.
+        ``transform``: apply this fitted / loaded ``ContentPCA`` instead of fitting.  Before the first use of the
+        engine only: its tables have the width it was built with.  Returns the ``ContentPCA``."""
+        from .reduce import ContentPCA
+        if self._engine is not None:
+            raise RuntimeError("reduce_content: this graph's engine exists already and its tables have the content's "
+                               "width; reduce the content before the first build_P / iterate / engine()")
+        if self._Z_host is not None:
+            raise RuntimeError("reduce_content: embeddings were set (set_Z / Vertex.z) at the content's width; reduce "
+                               "the content first")
+        pca = transform if transform is not None else ContentPCA(dim, center=center, whiten=whiten, block_rows=block_rows)
+        X = self.X if self.X.is_contiguous() else self.X.contiguous()
+        Y = pca.transform(X) if transform is not None else pca.fit_transform(X)
+        self.X, self.d, self.content_transform = Y.contiguous(), int(Y.shape[1]), pca
+        return pca
+
+    def project(self, dim: int = 2, table: str = "Z", vertices=None, whiten: bool = False):
+        """``(Y [len(vertices), dim] on the host in vertex order, the fitted ContentPCA)``: the principal components of
+        the CURRENT embeddings (``table="X"``: of the content) of ``vertices`` (default: all) -- the picture of an
+        embedding (extension).  Reads the engine's table where it lies and changes no state.  One GPU only."""
+        from .reduce import ContentPCA
+        eng = self.engine()
+        pca = ContentPCA(dim, whiten=whiten).fit_table(eng, table, vertices)
+        return pca.transform_table(eng, table, vertices).cpu(), pca
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

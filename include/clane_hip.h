@@ -62,7 +62,10 @@ extern "C" {
                              *    regressions, sigmoid loss / gradient and the top-k label masks fused into the logits'
                              *    contraction; workspaces and clane_probe_grad_* as for the soft-max probe)
                              *    + clane_embed_rows_* (new vertices embedded against the finished table: the per-row fixed
-                             *    point of build_P + update on frozen Z, one launch, every row stopping on its own) */
+                             *    point of build_P + update on frozen Z, one launch, every row stopping on its own)
+                             *    + clane_column_sums_*, clane_gram_*, clane_project_affine_*, clane_column_sums_ws_len,
+                             *    clane_gram_ws_len (content reduction: the device passes of a PCA on rows of a table --
+                             *    deterministic column sums, the centred Gram on the matrix cores, an affine projection) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -697,6 +700,51 @@ int clane_embed_rows_bf16(const int64_t *rowptr, const int32_t *colidx, int64_t 
                           const double *sums2, const float *sq, const float *S, int64_t lds, float gamma,
                           int32_t tolerence, int32_t max_rounds, int32_t flags, uint16_t *Z_out, int64_t ldo,
                           int32_t *rounds, float *delta, float *P_out, void *stream);
+
+/* ---- content reduction (csrc/content_pca.h) -----------------------------------------------------------------------------
+ * The device passes of a PCA on the rows `rows[0..n)` of the table Z [table_rows, ldz >= d].  The same calls serve a plain
+ * [n, d] matrix (rows = 0 .. n - 1) and an engine's permuted, padded table.  A rows entry outside [0, table_rows) is an
+ * ABSENT row: nothing is read for it, it adds nothing to the sums or the Gram, and its Y row is zeros.  Columns [d, ldz)
+ * are never read.  mu [d] (accumulate type) may be NULL: no centring.  flags: 0 or CLANE_PCA_ACCUMULATE.
+ *
+ * column_sums: sums[c] = sum_i Z[rows[i], c], in double.  Rows are taken in chunks of 2048: inside a chunk thread t of 16
+ *   adds rows t, t + 16, .. in row order and the 16 threads are added in thread order; the chunks' partials are added in
+ *   chunk order, starting from 0 or, with CLANE_PCA_ACCUMULATE, from the value already in sums -- so streaming a matrix
+ *   in blocks of a multiple of 2048 rows gives the bits of one call.  16-byte loads where Z and ldz allow them, single
+ *   elements otherwise: the same bits.  ws: clane_column_sums_ws_len(n, d) doubles.
+ * gram: G [d, d] contiguous (accumulate type) = sum_i (z_i - mu)(z_i - mu)^T, z - mu[col] formed in the accumulate type
+ *   by one subtraction.  Only the 128 x 128 tile pairs (ti <= tj) are computed, per chunk of 2048 rows; the chunks'
+ *   partials are added in chunk order (from 0, or from G with CLANE_PCA_ACCUMULATE, which must then be symmetric) and the
+ *   element of an off-diagonal pair is also written to G[j, i].  A (row, column) element's k terms run in the order of
+ *   the library's one tile contraction (mfma_slice) inside a chunk: on the same operands G has the bits of
+ *   clane_probe_grad_* called with its G = the centred rows ([n, d], accumulate type), its table = the same rows and
+ *   K = d.  G is bitwise symmetric.  ws: clane_gram_ws_len(n, d) elements of the accumulate type.
+ * project_affine: Y[i, 0:m) = W (z_rows[i] - mu), W [m, d] contiguous (accumulate type), Y [n, ldy >= m] in the TABLE
+ *   type, rounded once on the store; columns [m, ldy) of Y are not written.  On the same operands the accumulated value
+ *   has the bits of clane_project_rows_* on the centred table.
+ * No allocation, no synchronisation, no atomics on memory; two calls give the same bits. */
+#define CLANE_PCA_ACCUMULATE 1
+int clane_column_sums_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          int32_t flags, double *ws, double *sums, void *stream);
+int clane_column_sums_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          int32_t flags, double *ws, double *sums, void *stream);
+int clane_column_sums_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                           int32_t flags, double *ws, double *sums, void *stream);
+int64_t clane_column_sums_ws_len(int64_t n, int32_t d);
+int clane_gram_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                   const float *mu, int32_t flags, float *ws, float *G, void *stream);
+int clane_gram_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                   const double *mu, int32_t flags, double *ws, double *G, void *stream);
+int clane_gram_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                    const float *mu, int32_t flags, float *ws, float *G, void *stream);
+int64_t clane_gram_ws_len(int64_t n, int32_t d);
+int clane_project_affine_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const float *mu, const float *W, int32_t m, float *Y, int64_t ldy, void *stream);
+int clane_project_affine_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const double *mu, const double *W, int32_t m, double *Y, int64_t ldy, void *stream);
+int clane_project_affine_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
+                              int64_t n, const float *mu, const float *W, int32_t m, uint16_t *Y, int64_t ldy,
+                              void *stream);
 
 #ifdef __cplusplus
 }
