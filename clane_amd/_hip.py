@@ -69,6 +69,8 @@ for _s in ("f32", "f64", "bf16"):
         C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _p])
     SIGNATURES[f"clane_gather_rows_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p])
     SIGNATURES[f"clane_l1_distance_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p])
+SIGNATURES["clane_spmm_update_owned_f32"] = (
+    C.c_int, [_p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _p, _p])
 for _s in ("f32", "f64"):
     SIGNATURES[f"clane_degree_weighted_sums_{_s}"] = (C.c_int, [_p, _p, _p, _i64, _p, _p, _p])
     SIGNATURES[f"clane_edge_score_finalize_{_s}"] = (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p])
@@ -261,6 +263,62 @@ class DeviceBuffer:
             self.close()
         except Exception:       # interpreter shutdown: the process is about to give everything back anyway
             pass
+
+
+class _OwnedPlanStruct(C.Structure):    # clane_owned_plan_t
+    _fields_ = [(name, _p) for name in ("grp_bat_ptr", "bat_vrow_ptr", "bat_row_ptr", "bat_seg_ptr", "seg_e0", "seg_len",
+                                        "seg_vrow", "row_id", "row_part", "row_vptr")] + \
+               [(name, _i32) for name in ("n_groups", "n_steps", "chunk", "max_batch_vrows")]
+
+
+OWNED_PLAN_ARRAYS = {"grp_bat_ptr": torch.int32, "bat_vrow_ptr": torch.int32, "bat_row_ptr": torch.int32,
+                     "bat_seg_ptr": torch.int32, "seg_e0": torch.int64, "seg_len": torch.int32, "seg_vrow": torch.int32,
+                     "row_id": torch.int32, "row_part": torch.int32, "row_vptr": torch.int32}
+OWNED_MAX_STEPS = 64
+OWNED_LDS_LIMIT = 159 * 1024         # 160 KiB per CU less what the kernel keeps beside the sums
+
+
+class OwnedPlan:
+    """The plan of an spmm_update_owned call on the device (``clane_owned_plan_t``): `plan` is what
+    ``xcd.owned_plan`` returns (numpy), `chunk` the piece length.  Holds the arrays alive."""
+
+    def __init__(self, plan: dict, chunk: int, device):
+        self.n_groups, self.n_steps = int(plan["n_groups"]), int(plan["n_steps"])
+        self.chunk, self.max_batch_vrows = int(chunk), int(plan["max_batch_vrows"])
+        self.n_rows = int(plan["row_id"].shape[0])
+        self.arrays = {}
+        for name, dtype in OWNED_PLAN_ARRAYS.items():
+            t = torch.as_tensor(plan[name])
+            if t.dtype != dtype or t.dim() != 1:
+                raise ValueError(f"OwnedPlan: {name} must be a 1-D {dtype} array")
+            self.arrays[name] = t.contiguous().to(device)
+        a = {k: v.cpu() for k, v in self.arrays.items()}            # checked once, on the host: the kernel trusts them
+        B = a["bat_vrow_ptr"].numel() - 1
+        ok = (a["grp_bat_ptr"].numel() == self.n_groups + 1 and int(a["grp_bat_ptr"][0]) == 0
+              and int(a["grp_bat_ptr"][-1]) == B and bool((a["grp_bat_ptr"].diff() >= 0).all())
+              and a["bat_row_ptr"].numel() == B + 1 and a["bat_seg_ptr"].numel() == B * self.n_steps + 1
+              and int(a["bat_vrow_ptr"][0]) == 0 and int(a["bat_row_ptr"][0]) == 0 and int(a["bat_seg_ptr"][0]) == 0
+              and bool((a["bat_vrow_ptr"].diff() >= 0).all()) and bool((a["bat_row_ptr"].diff() >= 0).all())
+              and bool((a["bat_seg_ptr"].diff() >= 0).all()) and int(a["bat_row_ptr"][-1]) == self.n_rows
+              and a["row_vptr"].numel() == self.n_rows + 1 and a["row_part"].numel() == self.n_rows
+              and int(a["row_vptr"][0]) == 0 and bool((a["row_vptr"].diff() >= 1).all())
+              and int(a["row_vptr"][-1]) == int(a["bat_vrow_ptr"][-1])
+              and bool((a["row_vptr"][a["bat_row_ptr"].long()] == a["bat_vrow_ptr"]).all())
+              and int(a["bat_vrow_ptr"].diff().max() if B else 0) <= self.max_batch_vrows
+              and a["seg_e0"].numel() == a["seg_len"].numel() == a["seg_vrow"].numel() == int(a["bat_seg_ptr"][-1])
+              and 1 <= self.n_steps <= OWNED_MAX_STEPS and self.chunk >= 64 and self.chunk % 64 == 0)
+        if ok and a["seg_len"].numel():
+            per_batch = a["bat_seg_ptr"][self.n_steps::self.n_steps] - a["bat_seg_ptr"][:-1:self.n_steps]
+            seg_bat = torch.repeat_interleave(torch.arange(B), per_batch.long())
+            ok = bool((a["seg_len"] > 0).all()) and bool((a["seg_e0"] >= 0).all()) and bool((a["seg_vrow"] >= 0).all()) \
+                and bool((a["seg_vrow"] < a["bat_vrow_ptr"].diff()[seg_bat]).all())
+        if not ok:
+            raise ValueError("OwnedPlan: the arrays do not describe a plan (see include/clane_hip.h)")
+        self.max_edge = int((a["seg_e0"] + a["seg_len"]).max()) if a["seg_len"].numel() else 0
+        self.max_row = int(a["row_id"].max()) if self.n_rows else -1
+        self.max_part = int(a["row_part"].max()) if self.n_rows else -1
+        self.c = _OwnedPlanStruct(*[self.arrays[name].data_ptr() for name in OWNED_PLAN_ARRAYS], self.n_groups,
+                                  self.n_steps, self.chunk, self.max_batch_vrows)
 
 
 def _mirror_arg(mirror: Optional["Mirror"], dtype: torch.dtype):
@@ -515,6 +573,22 @@ class KernelBackend(abc.ABC):
         """Y[i, :m] = W (Z[rows[i], :d] - mu), W [m, d]; Y in Z's dtype, rounded once."""
         raise NotImplementedError(f"{type(self).__name__} has no project_affine")
 
+    # owned class rows (csrc/spmm_update.h, spmm_owned_kernel): optional in the same way -- a backend without them keeps
+    # every class row on spmm_update_class, and SweepEngine asks `has_spmm_owned` before it plans for them
+    def has_spmm_owned(self, dtype, d: int) -> bool:
+        """Whether spmm_update_owned has an instance for tables of `dtype` and rows of `d` elements."""
+        return False
+
+    def make_owned_plan(self, plan: dict, chunk: int, device):
+        """What spmm_update_owned takes as `plan`: xcd.owned_plan's arrays where the kernels read them."""
+        raise NotImplementedError(f"{type(self).__name__} has no make_owned_plan")
+
+    def spmm_update_owned(self, colidx, P, plan, block_threads: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
+                          partials, beyond_cache: bool = False, loads: int = 0):
+        """The class rows of `plan` summed in LDS by row-owning workgroups, then the usual epilogue; writes
+        partials[row_part[j]] for every row of the plan."""
+        raise NotImplementedError(f"{type(self).__name__} has no spmm_update_owned")
+
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
         pre-marshal it (HipKernels does)."""
@@ -756,6 +830,33 @@ class HipKernels(KernelBackend):
                      class_rows.numel(), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
                      SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0,
                      _vec(slab, acc_dtype(Z_old.dtype), "slab"), _mirror_arg(mirror, Z_new.dtype),
+                     _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+
+    def has_spmm_owned(self, dtype, d: int) -> bool:
+        return dtype == torch.float32 and 64 < d <= 256        # 16-byte packs at 32 or 64 lanes per row
+
+    def make_owned_plan(self, plan: dict, chunk: int, device) -> OwnedPlan:
+        return OwnedPlan(plan, chunk, device)
+
+    def spmm_update_owned(self, colidx, P, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X, gamma: float,
+                          Z_new, d: int, partials, beyond_cache: bool = False, loads: int = 0):
+        """Class rows summed in LDS by row-owning workgroups (no slab, no combine); writes partials[row_part[j]].
+        `loads`: CLANE_OWNED_LOADS, row loads in flight per wave (0 = the chunk kernel's choice)."""
+        zo, ldz = _mat(Z_old, "Z_old")
+        xp, ldx = _mat(X, "X")
+        zn, ldo = _mat(Z_new, "Z_new")
+        if not (Z_old.dtype == X.dtype == Z_new.dtype == torch.float32):
+            raise TypeError("spmm_update_owned: float32 tables only")
+        lanes = 32 if d <= 128 else 64
+        if plan.max_batch_vrows * lanes * 16 > OWNED_LDS_LIMIT:
+            raise ValueError(f"spmm_update_owned: {plan.max_batch_vrows} virtual rows per batch do not fit the LDS")
+        if (plan.max_edge > min(colidx.numel(), P.numel()) or plan.max_row >= min(X.shape[0], Z_new.shape[0])
+                or row0 + plan.max_row >= Z_old.shape[0] or plan.max_part >= partials.numel()):
+            raise ValueError("spmm_update_owned: the plan reaches outside colidx / P, the tables or the partials")
+        self._invoke(self.lib.clane_spmm_update_owned_f32, "clane_spmm_update_owned",
+                     _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
+                     int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
+                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8),
                      _vec(partials, torch.float64, "partials"), self._stream(Z_old))
 
     def reduce_partials(self, partials, n: int, ws, out):

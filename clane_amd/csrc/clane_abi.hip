@@ -520,6 +520,80 @@ int spmm_update_class(const int32_t *colidx, const PT *P, const int64_t *item_e0
     return check_launch("spmm_update_class");
 }
 
+// LDS of spmm_owned_kernel beyond its sums (the step counters), rounded up generously
+constexpr int64_t kOwnedLdsReserve = 1024;
+constexpr int64_t kLdsPerCU = 160 * 1024;
+constexpr int64_t kLdsDefaultLimit = 64 * 1024;
+
+template <typename T, typename PT>
+int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan, int32_t block_threads,
+                      int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
+                      typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t flags,
+                      double *delta_partials, void *stream) {
+    using A = typename Elem<T>::acc_t;
+    REQUIRE(plan, "spmm_update_owned: null plan");
+    REQUIRE(plan->n_groups >= 0 && row0 >= 0 && d > 0, "spmm_update_owned: bad shape");
+    REQUIRE(plan->n_steps >= 1 && plan->n_steps <= kOwnedMaxSteps, "spmm_update_owned: n_steps must be in [1, %d]",
+            kOwnedMaxSteps);
+    REQUIRE(plan->chunk >= kWave && plan->chunk % kWave == 0, "spmm_update_owned: chunk must be a positive multiple of 64");
+    REQUIRE(block_threads >= kWave && block_threads <= kOwnedMaxBlock && block_threads % kWave == 0,
+            "spmm_update_owned: block_threads must be a multiple of 64 in [64, %d]", kOwnedMaxBlock);
+    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_owned: leading dimension < d");
+    REQUIRE(plan->max_batch_vrows >= 0, "spmm_update_owned: negative max_batch_vrows");
+    if (plan->n_groups == 0) return CLANE_OK;
+    REQUIRE(colidx && P && plan->grp_bat_ptr && plan->bat_vrow_ptr && plan->bat_row_ptr && plan->bat_seg_ptr &&
+                plan->seg_e0 && plan->seg_len && plan->seg_vrow && plan->row_id && plan->row_part && plan->row_vptr &&
+                Z_old && X && Z_new && delta_partials,
+            "spmm_update_owned: null pointer");
+    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_owned: Z_new must not alias Z_old");
+    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new}, {ldz, ldx, ldo});
+    REQUIRE(L.vec && (L.lpr == 32 || L.lpr == 64) && d <= L.lpr * Elem<T>::kVec,
+            "spmm_update_owned: no instance for d=%d with these operands (16-byte packs, 17..64 packs per row)", d);
+    const int64_t lds = int64_t(plan->max_batch_vrows) * L.lpr * Elem<T>::kVec * int64_t(sizeof(A));
+    REQUIRE(lds + kOwnedLdsReserve <= kLdsPerCU, "spmm_update_owned: %lld virtual rows per batch need %lld bytes of LDS",
+            (long long)plan->max_batch_vrows, (long long)lds);
+    const OwnedPlan op{plan->grp_bat_ptr, plan->bat_vrow_ptr, plan->bat_row_ptr, plan->bat_seg_ptr, plan->seg_e0,
+                       plan->seg_len, plan->seg_vrow, plan->row_id, plan->row_part, plan->row_vptr, plan->n_steps,
+                       plan->chunk};
+    const bool beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
+    int rc = CLANE_OK;
+    auto launch = [&]<int VEC, int LPR, int U>() {
+        auto *kernel = spmm_owned_kernel<T, PT, VEC, LPR, U>;
+        if (lds > kLdsDefaultLimit) {      // above the default per-workgroup limit: ask for it, once per size
+            static int64_t granted = 0;
+            if (lds > granted) {
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+                if (e != hipSuccess) {
+                    rc = fail(CLANE_ERR_LAUNCH, "spmm_update_owned: %lld bytes of LDS: %s", (long long)lds,
+                              hipGetErrorString(e));
+                    return;
+                }
+                granted = lds;
+            }
+        }
+        kernel<<<unsigned(plan->n_groups), unsigned(block_threads), size_t(lds), (hipStream_t)stream>>>(
+            colidx, P, op, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, beyond, delta_partials);
+    };
+    constexpr int KV = Elem<T>::kVec;
+    // Row loads in flight per wave.  Asked for through CLANE_OWNED_LOADS(n) (the instances: 6, 8, 12 at two rows per
+    // instruction; 8, 12 at one), else the chunk kernel's: CLANE_CLASS_U32 at two rows per instruction beyond the caches.
+    const int asked = (flags >> 8) & 0xff;
+    REQUIRE(asked == 0 || asked == 8 || asked == 12 || (L.lpr == 32 && asked == 6),
+            "spmm_update_owned: no instance with %d row loads in flight", asked);
+    const int loads = asked ? asked : (L.lpr == 32 && beyond) ? CLANE_CLASS_U32 : CLANE_LONG_U;
+    if (L.lpr == 32) {
+        if (loads == 6) launch.template operator()<KV, 32, 6>();
+        else if (loads == 12) launch.template operator()<KV, 32, 12>();
+        else launch.template operator()<KV, 32, 8>();
+    } else {
+        if (loads == 12) launch.template operator()<KV, 64, 12>();
+        else launch.template operator()<KV, 64, 8>();
+    }
+    if (rc != CLANE_OK) return rc;
+    return check_launch("spmm_update_owned");
+}
+
 template <typename T>
 int l1_distance(const T *A, int64_t lda, const T *B, int64_t ldb, int64_t nrows, int32_t d,
                 typename Elem<T>::acc_t *sq_a, double *ws, double *out, void *stream) {
@@ -1242,6 +1316,13 @@ CLANE_CLASS_WRAPPER(f32, float, float, float, float)
 CLANE_CLASS_WRAPPER(f64, double, double, double, double)
 CLANE_CLASS_WRAPPER(bf16, uint16_t, bf16_t, float, float)
 #undef CLANE_CLASS_WRAPPER
+int clane_spmm_update_owned_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
+                                int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz, const float *X,
+                                int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d, int32_t flags,
+                                double *delta_partials, void *stream) {
+    return spmm_update_owned<float, float>(colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo,
+                                           d, flags, delta_partials, stream);
+}
 int64_t clane_spmm_class_slab_len(int64_t n_slots, int32_t d) { return n_slots * (ceil_div(d, 8) * 8); }
 int64_t clane_spmm_split_slab_len(int64_t n_segments, int32_t d) { return n_segments * (ceil_div(d, 8) * 8); }
 

@@ -872,5 +872,156 @@ __global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_kerne
     }
 }
 
+// ---- owned class rows: the sums never leave the CU ---------------------------------------------------------------
+// The chunk + combine pair above sends every partial sum of a class row through HBM (the slab) because the row's
+// chunks run on eight XCDs.  Here the XCD-private L2s get their disjoint working sets in TIME instead of in space: a
+// persistent workgroup (one per GROUP of the host's plan, clane_amd/xcd.py: owned_plan) owns a set of class rows for the
+// whole launch, keeps their sums in LDS and walks the (phase, class) STEPS in order -- every workgroup of the launch
+// gathers columns of the same step at about the same time, so each L2 holds that step's hot rows.  Nothing
+// synchronises the workgroups with each other: the plan deals the rows so that every group has about the same number of
+// edges, and that is all.
+//  * rows of more than `owned_row_edges` edges are cut by the plan into VIRTUAL rows with a sum of their own, so that
+//    several waves can work on one row within a step;
+//  * a group whose rows do not fit its LDS takes them in BATCHES, each through all steps;
+//  * inside a step the waves claim (virtual row, step) SEGMENTS from an LDS counter and request the next segment's
+//    first colidx / P before gathering the current one; a segment is walked in pieces of `chunk` edges, each from a
+//    zero register sum, added to the virtual row's LDS sum in piece order.  A virtual row has at most one segment per
+//    step, so one wave at a time touches a sum; one workgroup barrier separates the steps and EVERY wave reaches every
+//    barrier (the trip counts come from the plan);
+//  * after the last step a row's virtual rows are added in order and the usual epilogue runs, one partial per row as
+//    the combine kernel writes it.
+// A row's sum is: pieces from zero, added in (virtual row, step, piece) order -- fixed by the layout and the plan's
+// three constants, whatever the number of groups, the batch size, the workgroup size or the timing.
+constexpr int kOwnedMaxSteps = 64;      // (phase, class) keys: 8 classes x at most 8 phases
+constexpr int kOwnedMaxBlock = 1024;
+
+struct OwnedPlan {
+    const int32_t *grp_bat_ptr;   // [groups + 1]: a group's batches
+    const int32_t *bat_vrow_ptr;  // [batches + 1]: a batch's virtual rows (its LDS sums, in this order)
+    const int32_t *bat_row_ptr;   // [batches + 1]: a batch's rows
+    const int32_t *bat_seg_ptr;   // [batches * n_steps + 1]: the segments of (batch, step)
+    const int64_t *seg_e0;        // per segment: first edge, edges, virtual row within the batch
+    const int32_t *seg_len;
+    const int32_t *seg_vrow;
+    const int32_t *row_id;        // per row (batch order): row relative to the call's first row,
+    const int32_t *row_part;      //   its slot in the delta partials,
+    const int32_t *row_vptr;      //   [rows + 1] its virtual rows (numbered as bat_vrow_ptr numbers them)
+    int n_steps;
+    int chunk;
+};
+
+template <typename T, typename PT, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
+    const int32_t *__restrict__ colidx, const PT *__restrict__ P, OwnedPlan plan, int64_t row0,
+    const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma,
+    T *__restrict__ Znew, int64_t ldo, int d, bool nt_store, double *__restrict__ partials) {
+    using A = typename Elem<T>::acc_t;
+    constexpr int W = LPR * VEC;            // elements of one LDS sum: the whole row (the host checks d <= W)
+    constexpr int kRows = kWave / LPR;      // rows finished by one wave at a time
+    extern __shared__ __align__(16) unsigned char s_owned_raw[];
+    A *s_sum = reinterpret_cast<A *>(s_owned_raw);
+    __shared__ int s_cnt[kOwnedMaxSteps];
+
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const int nwaves = int(blockDim.x) / kWave;
+    const int sub = lane / LPR, sl = lane % LPR;
+    const int c0 = sl * VEC;
+    const bool col_ok = c0 < d;
+    const T *zcol = Zold + (col_ok ? c0 : 0);
+    const int n_steps = plan.n_steps;
+    const int64_t chunk = plan.chunk;
+    const int b0 = plan.grp_bat_ptr[blockIdx.x], b1 = plan.grp_bat_ptr[blockIdx.x + 1];
+
+    for (int b = b0; b < b1; ++b) {                          // uniform over the workgroup
+        const int v0 = plan.bat_vrow_ptr[b];
+        const int nv = plan.bat_vrow_ptr[b + 1] - v0;
+        for (int i = threadIdx.x; i < nv * W; i += int(blockDim.x)) s_sum[i] = A(0);
+        if (int(threadIdx.x) < n_steps) s_cnt[threadIdx.x] = 0;
+        __syncthreads();
+        for (int s = 0; s < n_steps; ++s) {
+            const int sa = plan.bat_seg_ptr[b * n_steps + s];
+            const int n = plan.bat_seg_ptr[b * n_steps + s + 1] - sa;
+            auto claim = [&]() -> int {
+                int v = 0;
+                if (lane == 0) v = atomicAdd(&s_cnt[s], 1);
+                return __builtin_amdgcn_readfirstlane(v);
+            };
+            int cur = claim();
+            int64_t e0 = 0, e1 = 0;
+            int vr = 0;
+            EdgeChunk<A> ch{0, A(0)};
+            if (cur < n) {
+                e0 = plan.seg_e0[sa + cur];
+                e1 = e0 + plan.seg_len[sa + cur];
+                vr = plan.seg_vrow[sa + cur];
+                ch = load_chunk<A, PT>(colidx, P, e0, e0 + chunk < e1 ? e0 + chunk : e1);
+            }
+            while (cur < n) {
+                const int nxt = claim();
+                int64_t n0 = 0, n1 = 0;
+                int vn = 0;
+                EdgeChunk<A> chn{0, A(0)};
+                if (nxt < n) {
+                    n0 = plan.seg_e0[sa + nxt];
+                    n1 = n0 + plan.seg_len[sa + nxt];
+                    vn = plan.seg_vrow[sa + nxt];
+                    chn = load_chunk<A, PT>(colidx, P, n0, n0 + chunk < n1 ? n0 + chunk : n1);
+                }
+                A *sum = s_sum + vr * W + c0;
+                for (int64_t p = e0; p < e1; p += chunk) {   // the segment's pieces, in order
+                    const int64_t pe = p + chunk < e1 ? p + chunk : e1;
+                    A acc[VEC];
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] = A(0);
+                    gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, p, pe, zcol, ldz, col_ok, acc, ch, p == e0);
+                    fold_subwaves<LPR>(acc);
+                    if (col_ok && sub == 0) {
+                        Pack<A, VEC> t = load_pack<A, VEC>(sum);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) t.v[k] += acc[k];
+                        store_pack<A, VEC>(sum, t);
+                    }
+                }
+                cur = nxt;
+                e0 = n0;
+                e1 = n1;
+                vr = vn;
+                ch = chn;
+            }
+            __syncthreads();                                  // the step is done in this workgroup
+        }
+        // the batch's rows: virtual rows added in order, then  z = x + gamma * sum,  delta, store
+        const int r0 = plan.bat_row_ptr[b];
+        const int nr = plan.bat_row_ptr[b + 1] - r0;
+        for (int j0 = wave * kRows; j0 < nr; j0 += nwaves * kRows) {     // uniform over the wave
+            const int j = j0 + sub;
+            const bool live = j < nr;
+            const bool ok = live && col_ok;
+            A rsum = A(0);
+            if (ok) {
+                const int64_t r = plan.row_id[r0 + j];
+                const Pack<T, VEC> x = load_pack_stream<T, VEC>(X + r * ldx + c0);
+                const Pack<T, VEC> zo = load_pack_stream<T, VEC>(Zold + (row0 + r) * ldz + c0);
+                const int va = plan.row_vptr[r0 + j] - v0, vb = plan.row_vptr[r0 + j + 1] - v0;
+                A acc[VEC];
+                const Pack<A, VEC> first = load_pack<A, VEC>(s_sum + va * W + c0);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) acc[k] = first.v[k];
+                for (int v = va + 1; v < vb; ++v) {
+                    const Pack<A, VEC> t = load_pack<A, VEC>(s_sum + v * W + c0);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] += t.v[k];
+                }
+                Pack<T, VEC> out{};
+                rsum = finish_pack<T, VEC>(x, zo, acc, gamma, true, Znew + r * ldo + c0, out, nt_store);
+            }
+            rsum = group_sum<LPR>(rsum);
+            if (live && sl == 0) partials[plan.row_part[r0 + j]] = double(rsum);
+        }
+        __syncthreads();                                      // the sums are read: the next batch may zero them
+    }
+}
+
 }  // namespace clane
 

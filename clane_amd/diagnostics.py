@@ -56,7 +56,8 @@ class DiagnosticsMixin:
         narrow = self.d > 0 and lanes_per_row(self.d_plan if len(self.tiles) > 1 else self.d, self.dtype) < 64
         return {"main": "spmm_update_subrow_kernel" if narrow else "spmm_update_kernel",
                 "mid": "spmm_long_kernel<4 waves>", "hub": "spmm_long_kernel<16 waves>",
-                "split": "spmm_class_chunk_kernel+combine" if self.class_threshold > 0
+                "split": ("spmm_owned_kernel+spmm_class_chunk_kernel+combine" if getattr(self, "class_owned", False)
+                          else "spmm_class_chunk_kernel+combine") if self.class_threshold > 0
                 else "spmm_split_segment_kernel+combine"}
 
     def estimated_sweep_seconds(self) -> float:
@@ -88,6 +89,12 @@ class DiagnosticsMixin:
                 "fewer_loads_in_flight": bool(self.beyond_cache and self.d > 0 and (str(self.dtype), lanes_per_row(
                     self.d_plan if len(self.tiles) > 1 else self.d, self.dtype)) in (("torch.float32", 32), ("torch.bfloat16", 16))),
                 "hot_rows_first": self.hot_rows_first, "exchange": self.exchange,
+                # only where the owned pass runs: measurements taken without it stay valid for engines without it
+                **({"class_owned": {"max_edges": self.owned_max_edges, "row_edges": self.owned_row_edges,
+                                    "groups": self.owned_groups, "block_threads": self.owned_block_threads,
+                                    "batch_vrows": self.owned_batch_vrows, "chunk": self.owned_chunk,
+                                    "loads": self.owned_loads}}
+                   if getattr(self, "class_owned", False) else {}),
                 }
 
     def exchange_bytes_per_sweep(self) -> int:

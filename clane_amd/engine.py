@@ -30,7 +30,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _hip, xcd
+from . import _hip, owned, xcd
 from .comm import TorchComm
 from .diagnostics import DiagnosticsMixin
 from .halo import build_halo_layout
@@ -64,7 +64,11 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                  overlap_chunks: bool = True, fused_pack: bool = True, class_threshold: Optional[int] = None,
                  class_chunk: int = CLASS_CHUNK, class_k1: bool = True, class_phases: Optional[int] = None,
                  phase_threshold: int = PHASE_THRESHOLD, delta_stream: bool = False, table_skew=None,
-                 table_alloc: str = "torch", column_tiles: Optional[int] = None):
+                 table_alloc: str = "torch", column_tiles: Optional[int] = None, class_owned: Optional[bool] = None,
+                 owned_max_edges: int = xcd.OWNED_MAX_EDGES, owned_row_edges: int = xcd.OWNED_ROW_EDGES,
+                 owned_groups: int = xcd.OWNED_GROUPS, owned_lds_bytes: int = xcd.OWNED_LDS_BYTES,
+                 owned_block_threads: int = xcd.OWNED_BLOCK_THREADS, owned_chunk: Optional[int] = None,
+                 owned_loads: int = xcd.OWNED_LOADS):
         """``exchange`` (N > 1 only) -- how the sweep is divided over the GPUs:
         "auto" (default) -- "columns" while a rank's slice of a row is >= 64 bytes, else "halo" (pick_exchange).
         "columns" -- every GPU holds the whole graph and d/N COLUMNS of X and Z.  ``Z[:, c] = X[:, c] + gamma P Z[:, c]``
@@ -75,6 +79,15 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         stores it into the tables of the ranks that read it (peer-to-peer over xGMI), there is no exchange step;
         "allgather" -- rows divided, full-size Z on every rank, in-place all-gather of the live rows
         (partition.py); "allgather_all" -- the same without the live/quiet split.
+        ``class_owned`` -- class rows of at most ``owned_max_edges`` edges are summed in LDS by row-owning workgroups
+        (spmm_update_owned: no slab, no combine pass) instead of chunk + combine; None = where it was measured to pay
+        (xcd.OWNED_DEFAULT: XCD-affine class rows of a table far beyond the Infinity Cache).  Taken
+        only where the kernel has an instance (one GPU, fp32, rows or column tiles of 65..256 elements); everything
+        else keeps chunk + combine, as do the rows above ``owned_max_edges``.  ``owned_row_edges``: rows above it
+        are cut into virtual rows; ``owned_groups`` workgroups of ``owned_block_threads`` threads, each with
+        ``owned_lds_bytes`` of LDS for its sums; ``owned_chunk``: piece length (None = ``class_chunk``); ``owned_loads``: row
+        loads in flight per wave (0 = as the chunk kernel).  Results depend on ``owned_max_edges``, ``owned_row_edges``
+        and ``owned_chunk`` alone.
         The constructor is a sequence of steps, each a method: the division over the ranks, the class-pass thresholds,
         the row layout, the row bins, the structure upload, the launch lists, the exchange lists, the tables, scratch."""
         if X.dim() != 2 or X.shape[0] != csr.num_vertices:
@@ -95,6 +108,9 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self._column_tiles_asked = column_tiles
         X = self._choose_division(csr, X, process_group, comm, exchange)
         self._choose_class_pass(csr, class_threshold, class_chunk, class_k1, class_phases, phase_threshold)
+        self._choose_owned(class_owned, owned_max_edges, owned_row_edges, owned_groups, owned_lds_bytes,
+                           owned_block_threads, owned_chunk)
+        self.owned_loads = int(owned_loads)
         self._build_layout(csr, chunks, shuffle, seed, hot_rows_first)
         self._choose_row_bins(long_threshold, hub_threshold)
         deg = self._upload_structure()
@@ -222,6 +238,33 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         # column, next to the other such rows' (xcd.class_items)
         self.mega_segment_edges = int(L2_BYTES_ALL_XCDS // 8 // max(row_bytes, 1)) if self.d_plan > 0 else 0
 
+    def _choose_owned(self, class_owned, max_edges, row_edges, groups, lds_bytes, block_threads, chunk) -> None:
+        """Whether the class rows of at most `max_edges` edges are summed by row-owning workgroups (xcd.owned_plan)."""
+        can = owned.possible(self)
+        want = (xcd.OWNED_DEFAULT and self.beyond_cache and self.class_affinity) if class_owned is None else bool(class_owned)
+        self.class_owned, self.owned_possible = bool(want and can), bool(can)
+        self._lds_bytes = int(lds_bytes)
+        self.owned_max_edges, self.owned_row_edges = int(max_edges), int(row_edges)
+        self.owned_groups, self.owned_block_threads = int(groups), int(block_threads)
+        self.owned_chunk = int(chunk) if chunk is not None else self.class_chunk
+        if self.class_owned:
+            self._check_owned_settings()
+
+    def _check_owned_settings(self) -> None:
+        widths = [c1 - c0 for c0, c1 in self.tiles]
+        if self.owned_groups < 1 or self.owned_row_edges < 64 or not (
+                64 <= self.owned_block_threads <= 1024 and self.owned_block_threads % 64 == 0):
+            raise ValueError("owned_groups must be >= 1, owned_row_edges >= 64, owned_block_threads a multiple of 64 "
+                             "in [64, 1024]")
+        if not (64 <= self.owned_chunk <= 4096 and self.owned_chunk % 64 == 0):
+            raise ValueError("owned_chunk must be a multiple of 64 in [64, 4096]")
+        # one LDS sum is a whole row of the lane layout: 32 or 64 lanes of 16 bytes
+        sum_bytes = 16 * lanes_per_row(max(widths), self.dtype)
+        self.owned_batch_vrows = self._lds_bytes // sum_bytes
+        if self.owned_batch_vrows < 1 or self.owned_batch_vrows * sum_bytes > _hip.OWNED_LDS_LIMIT:
+            raise ValueError(f"owned_lds_bytes must hold one sum of {sum_bytes} bytes and stay within "
+                             f"{_hip.OWNED_LDS_LIMIT}")
+
     def _build_layout(self, csr: HostCSR, chunks, shuffle, seed: int, hot_rows_first: bool) -> None:
         """Which rows this rank owns, where every row sits in the tables, the rank's CSR relabelled to table rows."""
         if chunks is None:
@@ -306,6 +349,10 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self.split_rows: List[Optional[tuple]] = []           # deg > SPLIT_EDGES: (rows, seg_ptr, seg_row) on device
         self.class_rows: List[Optional[tuple]] = []           # deg > class_threshold: (rows, slot_ptr, e0, len, slot, row)
         self.class_slots: List[int] = []                      # slot_ptr[-1] of each block's class rows, known on the host
+        # class_owned: per block (plan of the owned rows, launch lists of the class rows above owned_max_edges or None,
+        # number of those rows); the delta partials of a block's class rows are then [rows above, owned rows]
+        self.owned_rows: List[Optional[tuple]] = []
+        self._owned_inputs = {}
         self.k1_long_rows: List[Optional[torch.Tensor]] = []  # K1's workgroup-per-row list: above k1_threshold, not class
         self.split_edges = SPLIT_EDGES if split_hubs else 0
         hub_edges = int(deg[deg > SPLIT_EDGES].sum()) // max(1, len(self.blocks))
@@ -331,8 +378,13 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                               mega_min_edges=self.part.padded_vertices // 4)
                 # items per workgroup follow the item count (few chunks in a launch -- a chunk of a rank's rows --
                 # get smaller workgroups): class_items picks it after its one counting pass over the edges
+                segments = xcd.row_segments(self.local.rowptr, self.local.colidx, rows_abs, self.colidx,
+                                            self.phase_threshold, self.class_phases)
                 items = class_items(self.local.rowptr, self.local.colidx, rows_abs, self.class_chunk, None,
-                                    row_ids=rows_c, colidx_dev=self.colidx, **phased)
+                                    row_ids=rows_c, colidx_dev=self.colidx, segments=segments, **phased)
+                self.owned_rows.append(owned.plan_block(self, rows_c, rows_abs, segments, phased) if self.class_owned else None)
+                if self.owned_possible:             # set_owned() plans from these again
+                    self._owned_inputs[len(self.owned_rows) - 1] = (rows_c, rows_abs, segments, phased)
                 ipb = items["items_per_block"]
                 self.class_rows.append((to_dev(rows_c), torch.from_numpy(items["slot_ptr"]).to(dev),
                                         torch.from_numpy(items["e0"]).to(dev), torch.from_numpy(items["len"]).to(dev),
@@ -343,6 +395,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
             else:
                 self.class_rows.append(None)
                 self.class_slots.append(0)
+                self.owned_rows.append(None)
             k1_long = (db > self.k1_threshold) & ~(is_class if self.class_k1 else np.zeros_like(is_class)) \
                 if self.k1_threshold > 0 else np.zeros_like(is_class)
             self.k1_long_rows.append(to_dev(np.nonzero(k1_long)[0]))
@@ -368,6 +421,28 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         # one slab per launch stream: blocks alternate between two side streams when there are several
         self.slabs = [torch.zeros(slab_len, dtype=self.acc_dtype, device=dev)
                       for _ in range(2 if len(self.blocks) > 1 else 1)]
+
+    def set_owned(self, on: bool, **settings) -> None:
+        """Switch the owned pass on or off between sweeps, or plan it again with other settings (``max_edges``,
+        ``row_edges``, ``groups``, ``lds_bytes``, ``block_threads``, ``chunk``, ``loads``): for A/B timings on ONE engine's tables
+        (tools/owned_class_ab.py).  The edge order, P and build_P do not depend on any of it."""
+        if on and not self.owned_possible:
+            raise ValueError("this engine has no owned pass: one GPU, fp32, rows or tiles of 65..256 elements")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        for name, value in settings.items():
+            if name == "lds_bytes":
+                self._lds_bytes = int(value)
+            elif name in ("max_edges", "row_edges", "groups", "block_threads", "chunk", "loads"):
+                setattr(self, "owned_" + name, int(value))
+            else:
+                raise TypeError(f"set_owned: unknown setting {name!r}")
+        self.class_owned = bool(on)
+        if on:
+            self._check_owned_settings()
+        self.owned_rows = [owned.plan_block(self, *self._owned_inputs[i]) if on and i in self._owned_inputs else None
+                           for i in range(len(self.blocks))]
+        self._plans = {}
 
     def _setup_exchange(self, deg: np.ndarray, fused_pack: bool) -> None:
         """Halo exchange: send lists and send buffers (one per own chunk).  The kernel that finishes a row also stores
@@ -756,7 +831,18 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 if mir is not None and T > 1:
                     raise AssertionError("column tiles and mirrored launches do not combine")
                 for t in range(T):
-                    if self.class_rows[i] is not None:
+                    if self.owned_rows[i] is not None:      # the owned rows in LDS, the rows above them by chunk + combine
+                        plan, rest, _ = self.owned_rows[i]
+                        steps.append(("call", owned.bind_launch(self, plan, b.row0, cut(Zold, t), cut(Xb, t), gamma,
+                                                                cut(Zn, t), width(t), part(po_class, t))))
+                        if rest is not None:
+                            rows_r, slot_ptr, it_e0, it_len, it_slot, ipb = rest
+                            steps.append(("call", self._bind("spmm_update_class", self.colidx, self.P, it_e0, it_len,
+                                                             it_slot, ipb, rows_r, slot_ptr, b.row0, cut(Zold, t),
+                                                             cut(Xb, t), gamma, cut(Zn, t), width(t),
+                                                             self.slabs[i % len(self.slabs)], part(po_class, t),
+                                                             mirror=mir, beyond_cache=self.beyond_cache)))
+                    elif self.class_rows[i] is not None:
                         rows_c, slot_ptr, it_e0, it_len, it_slot, _, ipb = self.class_rows[i]
                         steps.append(("call", self._bind("spmm_update_class", self.colidx, self.P, it_e0, it_len, it_slot,
                                                          ipb, rows_c, slot_ptr, b.row0, cut(Zold, t), cut(Xb, t), gamma,

@@ -91,7 +91,8 @@ def row_pieces(rowptr: np.ndarray, max_edges: int):
 
 def class_items(rowptr: np.ndarray, colidx: np.ndarray, rows: np.ndarray, chunk: int, items_per_block: Optional[int],
                 row_ids: Optional[np.ndarray] = None, colidx_dev: Optional[torch.Tensor] = None,
-                phase_threshold: int = 0, phases: int = 1, mega_segment_edges: int = 0, mega_min_edges: int = 0) -> dict:
+                phase_threshold: int = 0, phases: int = 1, mega_segment_edges: int = 0, mega_min_edges: int = 0,
+                segments=None) -> dict:
     """Work items of the XCD-affine pass over `rows` (absolute local row ids whose edges are sorted by
     (xcd_class(column), column)): every class segment of a row is cut into chunks of at most `chunk` edges.
     Slots -- where the partial sums go -- are numbered row by row, class by class, chunk by chunk, so a row's slots
@@ -102,37 +103,12 @@ def class_items(rowptr: np.ndarray, colidx: np.ndarray, rows: np.ndarray, chunk:
     8-block rounds, so block index % 8 stays the class), then the blocks of the other rows.  Inside a class the items go row
     by row, except those of mega rows (`mega_segment_edges`), which come first ordered by their first column.  Returns int64 e0, int32 len, int32 slot, int32 row (flat, whole blocks; row = `row_ids` of the
     item's row, default `rows` itself), int64 slot_ptr [rows + 1] and the items_per_block used (None on entry: chosen
-    by `items_per_block_for` from the item count, once the O(E) counting pass has it -- the layout itself is cheap)."""
+    by `items_per_block_for` from the item count, once the O(E) counting pass has it -- the layout itself is cheap).
+    `segments`: what `row_segments` returns for these rows, for a caller that has it already."""
     n = rows.size
     NS = XCD_CLASSES * max(1, phases)                       # sub-classes per row (phase-major)
-    sizes = (rowptr[rows + 1] - rowptr[rows]).astype(np.int64)
-    start = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-    if colidx_dev is not None and colidx_dev.is_cuda:        # the O(E) part on the card (40M edges: 0.3 s on the host)
-        dev = colidx_dev.device
-        seg_len = np.empty(n * NS, dtype=np.int64)
-        unsorted = False
-        bounds = np.concatenate([[0], np.cumsum(sizes)])
-        for a, b in row_pieces(bounds, CLASS_ITEMS_PIECE_EDGES):    # pieces bound the scratch memory on the card
-            if bounds[b] == bounds[a]:
-                seg_len[a * NS:b * NS] = 0
-                continue
-            sizes_t = torch.from_numpy(sizes[a:b]).to(dev)
-            rid = torch.repeat_interleave(torch.arange(b - a, device=dev), sizes_t)
-            idx = (torch.from_numpy(rowptr[rows[a:b]] - (start[a:b] - bounds[a])).to(dev)[rid]
-                   + torch.arange(int(bounds[b] - bounds[a]), device=dev))
-            sub = xcd_subclass(colidx_dev[idx].long(), sizes_t[rid], 0, phase_threshold, phases)
-            key = rid * NS + sub
-            unsorted = unsorted or (bool((key[1:] < key[:-1]).any()) if key.numel() > 1 else False)
-            seg_len[a * NS:b * NS] = torch.bincount(key, minlength=(b - a) * NS).cpu().numpy()
-    else:
-        idx = np.repeat(rowptr[rows] - start, sizes) + np.arange(int(sizes.sum()), dtype=np.int64)
-        rid = np.repeat(np.arange(n, dtype=np.int64), sizes)
-        sub = xcd_subclass(colidx[idx].astype(np.int64), sizes[rid], 0, phase_threshold, phases)
-        unsorted = idx.size > 1 and bool((np.diff(rid * NS + sub) < 0).any())
-        seg_len = np.bincount(rid * NS + sub, minlength=n * NS)
-    if unsorted:
-        raise AssertionError("class rows must have their edges sorted by (xcd_subclass(column), column)")
-    seg_e0 = np.repeat(rowptr[rows], NS) + (np.cumsum(seg_len) - seg_len - np.repeat(start, NS))
+    sizes, seg_len, seg_e0 = segments if segments is not None else \
+        row_segments(rowptr, colidx, rows, colidx_dev, phase_threshold, phases)
     nchunk = -(-seg_len // chunk)
     tot = int(nchunk.sum())
     if items_per_block is None:
@@ -193,8 +169,164 @@ def class_items(rowptr: np.ndarray, colidx: np.ndarray, rows: np.ndarray, chunk:
             "items_per_block": int(items_per_block)}
 
 
+def row_segments(rowptr: np.ndarray, colidx: np.ndarray, rows: np.ndarray, colidx_dev: Optional[torch.Tensor] = None,
+                 phase_threshold: int = 0, phases: int = 1):
+    """The (phase, class) segments of `rows` (absolute local row ids whose edges are sorted by
+    (xcd_subclass(column), column); AssertionError otherwise): the rows' edge counts [n], the segments' lengths and
+    first edges [n * NS], NS = 8 * phases, row-major then phase-major.  One O(E) counting pass, on the card when
+    `colidx_dev` is there."""
+    n = rows.size
+    NS = XCD_CLASSES * max(1, phases)                       # sub-classes per row (phase-major)
+    sizes = (rowptr[rows + 1] - rowptr[rows]).astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    if colidx_dev is not None and colidx_dev.is_cuda:        # the O(E) part on the card (40M edges: 0.3 s on the host)
+        dev = colidx_dev.device
+        seg_len = np.empty(n * NS, dtype=np.int64)
+        unsorted = False
+        bounds = np.concatenate([[0], np.cumsum(sizes)])
+        for a, b in row_pieces(bounds, CLASS_ITEMS_PIECE_EDGES):    # pieces bound the scratch memory on the card
+            if bounds[b] == bounds[a]:
+                seg_len[a * NS:b * NS] = 0
+                continue
+            sizes_t = torch.from_numpy(sizes[a:b]).to(dev)
+            rid = torch.repeat_interleave(torch.arange(b - a, device=dev), sizes_t)
+            idx = (torch.from_numpy(rowptr[rows[a:b]] - (start[a:b] - bounds[a])).to(dev)[rid]
+                   + torch.arange(int(bounds[b] - bounds[a]), device=dev))
+            sub = xcd_subclass(colidx_dev[idx].long(), sizes_t[rid], 0, phase_threshold, phases)
+            key = rid * NS + sub
+            unsorted = unsorted or (bool((key[1:] < key[:-1]).any()) if key.numel() > 1 else False)
+            seg_len[a * NS:b * NS] = torch.bincount(key, minlength=(b - a) * NS).cpu().numpy()
+    else:
+        idx = np.repeat(rowptr[rows] - start, sizes) + np.arange(int(sizes.sum()), dtype=np.int64)
+        rid = np.repeat(np.arange(n, dtype=np.int64), sizes)
+        sub = xcd_subclass(colidx[idx].astype(np.int64), sizes[rid], 0, phase_threshold, phases)
+        unsorted = idx.size > 1 and bool((np.diff(rid * NS + sub) < 0).any())
+        seg_len = np.bincount(rid * NS + sub, minlength=n * NS)
+    if unsorted:
+        raise AssertionError("class rows must have their edges sorted by (xcd_subclass(column), column)")
+    seg_e0 = np.repeat(rowptr[rows], NS) + (np.cumsum(seg_len) - seg_len - np.repeat(start, NS))
+    return sizes, seg_len.astype(np.int64), seg_e0
+
+
 def items_per_block_for(n_items: int) -> int:
     """Chunks per workgroup of the class kernels: CLASS_ITEMS_PER_BLOCK when there are plenty, fewer (down to one per
     wave) when a launch holds few chunks -- a launch wants >= ~4096 workgroups to fill 256 CUs (a rank's quarter of
     the halo split at 8 GPUs holds 21k chunks: 650 workgroups of 32 ran at a third of the rate of 2 600 of 8)."""
     return int(min(CLASS_ITEMS_PER_BLOCK, max(4, 4 * -(-n_items // (4 * 4096)))))
+
+
+# ---- owned class rows: the plan of spmm_owned_kernel (csrc/spmm_update.h) -------------------------------------------
+# Class rows of at most OWNED_MAX_EDGES edges are summed by row-owning workgroups instead of chunk + combine: a
+# workgroup keeps the sums of its rows in LDS and walks the rows' (phase, class) segments step by step, so nothing goes
+# through a slab.  Measured on R-MAT 2M / 40M / d = 256 in two column tiles, one engine, variants alternating
+# (profiles/r06_owned_class_pass.md; sweep ms, chunk + combine 3.623):
+#  * what decides is how many BATCHES a group needs and how far the groups drift apart: 512 groups of 768 threads with
+#    72 KiB each (two batches, 3 % step spread) 3.79; 256 groups of 1024 threads with 144 KiB (two batches, 2 %) 3.62;
+#  * all class rows up to 4096 edges are 92 k sums of 512 bytes = 47 MB, more than the 40 MB of LDS on the card: two
+#    batches at best, and 16 steps (the rows above PHASE_THRESHOLD are phased).  The 74.7 k rows up to 512 edges fit ONE
+#    batch of 152 KiB per CU and have 8 steps, dealt to 0.4 % per step: 3.56;
+#  * 16 waves per CU leave registers for 12 row loads in flight per wave: 3.52 (8: 3.55 at two batches; 6: 3.56 / 3.62).
+# Rows above OWNED_ROW_EDGES edges would be cut into virtual rows (several waves per row and step): none at 512.
+OWNED_MAX_EDGES = 512
+OWNED_ROW_EDGES = 1024
+OWNED_GROUPS = 256               # one workgroup per CU ...
+OWNED_BLOCK_THREADS = 1024       # ... of 16 waves
+OWNED_LDS_BYTES = 152 * 1024     # its sums: 304 rows of 512 bytes
+OWNED_LOADS = 12                 # row loads in flight per wave (CLANE_OWNED_LOADS), 0 = as the chunk kernel
+# SweepEngine(class_owned=None): on where it was measured to pay -- XCD-affine class rows of a table far beyond the
+# Infinity Cache (engine.beyond_cache), where the kernel has an instance.  A cache-resident table (config 2) or evenly
+# spread reads keep chunk + combine: not measured to gain, so not switched.
+OWNED_DEFAULT = True
+
+
+def owned_plan(sizes: np.ndarray, seg_len: np.ndarray, seg_e0: np.ndarray, row_ids: np.ndarray, row_parts: np.ndarray,
+               *, row_edges: int, groups: int, batch_vrows: int) -> Optional[dict]:
+    """Plan of the owned pass over n rows given by `row_segments` (sizes [n], seg_len / seg_e0 [n * NS]); `row_ids`:
+    the rows relative to the launch's first row, `row_parts`: their slots in the delta partials.
+
+    STEPS are the (phase, class) keys that hold any edge, in increasing order.  A row of more than `row_edges` edges is
+    cut into VIRTUAL rows of at most that many, evenly over the keys: virtual row j of nv takes the edges
+    [j L / nv, (j + 1) L / nv) of every segment of L edges.  Rows (with all their virtual rows) are dealt to `groups`
+    groups, heaviest first, each to the group whose cumulative edges stay lowest against the fair share at every step
+    (lowest index on a tie): the groups then change step at about the same time.  A
+    group takes its rows, in the order dealt, in consecutive BATCHES of at most `batch_vrows` virtual rows.  Returns
+    the flat arrays of clane_owned_plan_t (include/clane_hip.h) plus `group_step_edges` [groups, steps] for whoever
+    wants to look at the balance; None without rows.  The order in which a row's edges are summed -- (virtual row,
+    step, piece) -- does not depend on `groups` or `batch_vrows`."""
+    n = int(sizes.size)
+    if n == 0:
+        return None
+    if groups < 1 or row_edges < 64:
+        raise ValueError("owned_plan: groups must be >= 1 and row_edges >= 64")
+    NS = seg_len.size // n
+    seg_len = seg_len.reshape(n, NS).astype(np.int64)
+    seg_e0 = seg_e0.reshape(n, NS).astype(np.int64)
+    keys = np.nonzero(seg_len.sum(0) > 0)[0]
+    if keys.size == 0:
+        keys = np.zeros(1, dtype=np.int64)
+    S = int(keys.size)
+    seg_len, seg_e0 = seg_len[:, keys], seg_e0[:, keys]
+    # virtual rows: as few as keep every one of them within row_edges (the bound: a share of L edges is <= ceil(L / nv))
+    nv = np.maximum(1, -(-sizes // row_edges)).astype(np.int64)
+    while True:
+        over = (-(-seg_len // nv[:, None])).sum(1) > row_edges
+        if not over.any():
+            break
+        nv[over] += 1
+    if int(nv.max()) > batch_vrows:
+        raise ValueError(f"owned_plan: a row of {int(nv.max())} virtual rows does not fit a batch of {batch_vrows}")
+    # The deal: heaviest row first, to the group that stays furthest below its share at EVERY step.  What costs hit rate
+    # is drift -- a group that is ahead or behind in edges when the others change step -- so a group's load is its
+    # cumulative edges after each step over that step's fair share, and a row goes where the largest of them ends lowest.
+    row_cum = np.cumsum(seg_len, 1).astype(np.float64)
+    share = np.maximum(row_cum.sum(0) / groups, 1.0)
+    row_cum /= share
+    cum = np.zeros((groups, S))
+    group_of = np.empty(n, dtype=np.int64)
+    dealt = np.argsort(-sizes, kind="stable")
+    for i in dealt.tolist():
+        g = int((cum + row_cum[i]).max(1).argmin())
+        group_of[i] = g
+        cum[g] += row_cum[i]
+    order = dealt[np.argsort(group_of[dealt], kind="stable")]         # by group, inside a group as dealt
+    g_sorted, nv_sorted = group_of[order], nv[order]
+    bat_of_row = np.empty(n, dtype=np.int64)
+    b, used, g_prev = -1, 0, -1
+    for j, (g, k) in enumerate(zip(g_sorted.tolist(), nv_sorted.tolist())):
+        if g != g_prev or used + k > batch_vrows:
+            b, used, g_prev = b + 1, 0, g
+        used += k
+        bat_of_row[j] = b
+    B = b + 1
+    bat_row_ptr = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(np.bincount(bat_of_row, minlength=B), out=bat_row_ptr[1:])
+    row_vptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nv_sorted, out=row_vptr[1:])
+    bat_vrow_ptr = row_vptr[bat_row_ptr]
+    bat_group = g_sorted[bat_row_ptr[:-1]]
+    grp_bat_ptr = np.zeros(groups + 1, dtype=np.int64)
+    np.cumsum(np.bincount(bat_group, minlength=groups), out=grp_bat_ptr[1:])
+    # the virtual rows' shares of every step, in the new order
+    nvirt = int(row_vptr[-1])
+    v_row = np.repeat(np.arange(n), nv_sorted)                         # position of the row in `order`
+    v_j = np.arange(nvirt) - row_vptr[v_row]
+    L, E0, NV = seg_len[order][v_row], seg_e0[order][v_row], nv_sorted[v_row][:, None]
+    lo = (v_j[:, None] * L) // NV
+    hi = ((v_j[:, None] + 1) * L) // NV
+    v_len, v_e0 = hi - lo, E0 + lo
+    v_idx, s_idx = np.nonzero(v_len > 0)
+    v_bat = bat_of_row[v_row]
+    key = v_bat[v_idx] * S + s_idx
+    by = np.lexsort((v_idx, key))                                      # (batch, step), then virtual row
+    v_idx, s_idx, key = v_idx[by], s_idx[by], key[by]
+    bat_seg_ptr = np.zeros(B * S + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key, minlength=B * S), out=bat_seg_ptr[1:])
+    group_step = np.zeros((groups, S), dtype=np.int64)
+    np.add.at(group_step, (g_sorted[v_row][v_idx], s_idx), v_len[v_idx, s_idx])
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)            # noqa: E731
+    return {"grp_bat_ptr": i32(grp_bat_ptr), "bat_vrow_ptr": i32(bat_vrow_ptr), "bat_row_ptr": i32(bat_row_ptr),
+            "bat_seg_ptr": i32(bat_seg_ptr), "seg_e0": np.ascontiguousarray(v_e0[v_idx, s_idx], dtype=np.int64),
+            "seg_len": i32(v_len[v_idx, s_idx]), "seg_vrow": i32(v_idx - bat_vrow_ptr[v_bat[v_idx]]),
+            "row_id": i32(row_ids[order]), "row_part": i32(row_parts[order]), "row_vptr": i32(row_vptr),
+            "n_groups": int(groups), "n_steps": S, "max_batch_vrows": int(np.diff(bat_vrow_ptr).max()),
+            "steps": keys.astype(np.int64), "group_step_edges": group_step}

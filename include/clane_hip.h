@@ -65,7 +65,9 @@ extern "C" {
                              *    point of build_P + update on frozen Z, one launch, every row stopping on its own)
                              *    + clane_column_sums_*, clane_gram_*, clane_project_affine_*, clane_column_sums_ws_len,
                              *    clane_gram_ws_len (content reduction: the device passes of a PCA on rows of a table --
-                             *    deterministic column sums, the centred Gram on the matrix cores, an affine projection) */
+                             *    deterministic column sums, the centred Gram on the matrix cores, an affine projection)
+                             *    + clane_spmm_update_owned_f32 (class rows summed in LDS by row-owning workgroups: no slab,
+                             *    no combine pass; embedder.py:90-92) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -341,6 +343,58 @@ int clane_spmm_update_class_bf16(const int32_t *colidx, const float *P, const in
                                  const uint16_t *Z_old, int64_t ldz, const uint16_t *X, int64_t ldx, float gamma,
                                  uint16_t *Z_new, int64_t ldo, int32_t d, int32_t flags, float *slab, const clane_mirror_t *mirror,
                                  double *delta_partials, void *stream);
+
+/*  clane_spmm_update_owned_f32 : class rows whose sums never leave the CU (the reference's loop is embedder.py:90-92
+ *                             for every row alike; no counterpart of the schedule).  clane_spmm_update_class_* sends
+ *                             every partial sum of a row through `slab`, because the row's items run on eight XCDs.
+ *                             Here one persistent workgroup per GROUP owns a set of the rows for the whole launch,
+ *                             keeps their sums in LDS and walks the rows' (phase, class) segments STEP by step: all
+ *                             groups gather columns of the same step at about the same time, so each XCD's L2 holds
+ *                             that step's hot rows -- in time what the item blocks above do in space.  Nothing
+ *                             synchronises the groups; the caller deals the rows so that the groups' edges agree.
+ *                             The plan (device arrays, built by the caller: clane_amd/xcd.py owned_plan):
+ *                             a row of many edges is cut into VIRTUAL rows, each with an LDS sum of its own; group g
+ *                             takes its rows in the batches [grp_bat_ptr[g], grp_bat_ptr[g+1]), each through all
+ *                             n_steps steps; batch b holds the virtual rows [bat_vrow_ptr[b], bat_vrow_ptr[b+1]) (at
+ *                             most max_batch_vrows) and the rows [bat_row_ptr[b], bat_row_ptr[b+1]); the segments of
+ *                             (batch b, step s) are [bat_seg_ptr[b n_steps + s], bat_seg_ptr[b n_steps + s + 1]):
+ *                             seg_e0 / seg_len an edge range in colidx / P, seg_vrow the virtual row WITHIN the batch
+ *                             (at most one segment per virtual row and step).  A segment is gathered in pieces of
+ *                             `chunk` edges (a multiple of 64), each from zero, added to the virtual row's sum in
+ *                             order.  Row j (batch order) is local row row_id[j], its virtual rows are
+ *                             [row_vptr[j], row_vptr[j+1]) and are added in that order, then the usual epilogue; its
+ *                             |delta| goes to delta_partials[row_part[j]].  So a row's sum is fixed by the plan's
+ *                             (virtual row, step, piece) order alone: the number of groups, the batches, block_threads
+ *                             and the timing do not change a bit.
+ *                             block_threads: 64..1024, a multiple of 64.  d must fit one pass of the lane layout (fp32,
+ *                             16-byte packs: d <= 256) and Z_old / X / Z_new must allow 16-byte packs; anything else
+ *                             is CLANE_ERR_INVALID_ARGUMENT -- the caller keeps clane_spmm_update_class_* for it, as
+ *                             for bf16 / fp64 tables and mirrored launches.  max_batch_vrows LDS sums of a whole row
+ *                             (512 bytes up to d = 128, else 1 KiB) must fit 160 KiB less 1 KiB.
+ *                             flags: CLANE_SPMM_TABLE_BEYOND_CACHE or 0, and CLANE_OWNED_LOADS(n): n row loads in flight
+ *                             per wave (6, 8, 12 up to d = 128; 8, 12 above; 0 = the chunk kernel's choice).  Neither
+ *                             changes a result. */
+#define CLANE_OWNED_LOADS(n) (((n) & 0xff) << 8)
+typedef struct {
+    const int32_t *grp_bat_ptr;
+    const int32_t *bat_vrow_ptr;
+    const int32_t *bat_row_ptr;
+    const int32_t *bat_seg_ptr;
+    const int64_t *seg_e0;
+    const int32_t *seg_len;
+    const int32_t *seg_vrow;
+    const int32_t *row_id;
+    const int32_t *row_part;
+    const int32_t *row_vptr;
+    int32_t n_groups;
+    int32_t n_steps;
+    int32_t chunk;
+    int32_t max_batch_vrows;
+} clane_owned_plan_t;
+int clane_spmm_update_owned_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
+                                int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz, const float *X,
+                                int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d, int32_t flags,
+                                double *delta_partials, void *stream);
 
 /* out[0] = sum of partials[0..n) in a fixed order (bitwise reproducible).  Finishes embedder.py:94 / :60.
  * ws: clane_reduce_ws_len() doubles. */
