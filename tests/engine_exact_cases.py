@@ -16,6 +16,9 @@ Every check takes the kernel object and the device: HipKernels on the card, the 
 check collects its named comparisons in a `Checks` and asserts that none failed; every comparison is torch.equal or ==.
 Nothing here has a tolerance.
 
+`OWNED_PLANS` puts the class rows of the one-GPU plans through the owned pass (spmm_owned_kernel: fp32 only, hence a
+list of its own), down to the configuration the engine chooses by itself for a table beyond the Infinity Cache.
+
 Combinations the engine refuses by design, hence not run: column tiles under any division (engine.py,
 _choose_division: ``T = self._pick_tiles(csr, X.dtype) if not divided else 1`` -- a division ignores ``column_tiles``;
 _build_plan: "column tiles and mirrored launches do not combine").
@@ -27,9 +30,11 @@ import threading
 import numpy as np
 import torch
 
-from clane_amd import _hip
+import clane_amd.engine as engine_module
+from clane_amd import _hip, xcd
 from clane_amd.engine import SPLIT_EDGES, SweepEngine
 from clane_amd.partition import HostCSR
+from clane_amd.plan import lanes_per_row
 from oracle import clane_oracle as O
 
 from . import exact_cases as E
@@ -365,11 +370,12 @@ def plan_id(run):
     return f"{case_id(run[0])}-{run[1]}"
 
 
-def run_plan(kernels, dev, c, settings, route, tag):
-    """One engine, one sweep: the `Checks` of check A."""
+def run_plan(kernels, dev, c, settings, route, tag, constructing=contextlib.nullcontext):
+    """One engine, one sweep: the `Checks` of check A.  `constructing`: a context for the engine's construction."""
     checks = Checks(tag)
     with device_ctx(dev):
-        eng = make_engine(kernels, dev, c, **settings)
+        with constructing():
+            eng = make_engine(kernels, dev, c, **settings)
         route(eng, dev)
         judge_one_sweep(checks, c, one_sweep(eng, c))
     return checks
@@ -378,6 +384,158 @@ def run_plan(kernels, dev, c, settings, route, tag):
 def check_plan(kernels, dev, case, plan):
     settings, route = PLANS[plan]
     run_plan(kernels, dev, engine_case(*case), settings, route, plan_id((case, plan))).assert_none_failed()
+
+
+# ---- A': the owned class pass (csrc/spmm_update.h spmm_owned_kernel) under the engine's plans ------------------------
+# Apart from PLANS / PLAN_RUNS, which tests/consumer_exact_cases.py and OTHER_PLANS also run at bf16 and fp64, where the
+# owned pass has no instance.  Judged like every plan of A.  8 groups with 8 LDS sums each: the 103 rows above 32 edges
+# need up to 3 batches per group; the 700-edge row is 6 virtual rows of at most 128 edges (4 sums per batch could not
+# hold it: xcd.owned_plan refuses).
+OWN = dict(class_owned=True, owned_groups=8, owned_block_threads=256, owned_row_edges=128, owned_max_edges=4096)
+OWNED_SUMS = 8
+CHUNKS3_GROUPS = 3              # some 35 class rows per block of 234: 3 groups of 8 sums need 2 batches in every block
+
+
+def own(*base, width=128, **more):
+    """OWN, the LDS of OWNED_SUMS sums of rows (or column tiles) of `width` fp32 elements, and what the plan adds."""
+    out = dict(OWN, owned_lds_bytes=OWNED_SUMS * 16 * lanes_per_row(width, F32))
+    for b in base:
+        out.update(b)
+    out.update(more)
+    return out
+
+
+@contextlib.contextmanager
+def no_infinity_cache():
+    """While an engine is constructed: its planning sees an Infinity Cache of no bytes, so every table is beyond it.
+    Put back on the way out; the engine keeps what it chose."""
+    kept = engine_module.INFINITY_CACHE_BYTES
+    engine_module.INFINITY_CACHE_BYTES = 0
+    try:
+        yield
+    finally:
+        engine_module.INFINITY_CACHE_BYTES = kept
+
+
+def plan_field(plan, name):
+    """A field of a block's owned plan: xcd.owned_plan's dict on the double, _hip.OwnedPlan on the card."""
+    if isinstance(plan, dict):
+        return plan[name]
+    return plan.arrays[name].cpu().numpy() if name in plan.arrays else getattr(plan, name)
+
+
+def batches_per_group(plan):
+    return np.diff(plan_field(plan, "grp_bat_ptr"))
+
+
+def _route_owned(blocks=1, n_rest=0, batches=2, hot=True, tiles=1, steps=None, more=None):
+    """EVERY block has an owned plan, with `n_rest` class rows beside it on chunk + combine; some group
+    takes its rows in at least `batches` batches; the vertex order is the engine's own (`hot`) or a shuffled one."""
+    def route(eng, dev):
+        assert eng.class_owned and len(eng.blocks) == blocks and all(o is not None for o in eng.owned_rows)
+        plans = [o[0] for o in eng.owned_rows]
+        for _, rest, n in eng.owned_rows:
+            assert (rest is not None) == (n > 0) and n == n_rest
+        assert max(int(batches_per_group(p).max()) for p in plans) >= batches
+        assert all(plan_field(p, "n_groups") == eng.owned_groups for p in plans) and len(eng.tiles) == tiles
+        assert eng.hot_rows_first == hot and not bool((eng.pos.cpu() == torch.arange(eng.V)).all())
+        if steps is not None:
+            assert [plan_field(p, "n_steps") for p in plans] == steps
+        if more is not None:
+            more(eng, plans)
+    return route
+
+
+def _owned_class(eng, plans):
+    assert plan_field(plans[0], "row_id").size == 103 and int(batches_per_group(plans[0]).max()) == 3
+    nv = np.diff(plan_field(plans[0], "row_vptr"))
+    assert sorted(nv[nv > 1].tolist()) == [2, 3, 6, 6]                # the rows of 129, 300, 650 and 700 edges
+
+
+def _owned_phases2(eng, plans):
+    assert (eng.class_phases, eng.phase_threshold) == (2, 128)
+
+
+def _owned_chunk256(eng, plans):
+    assert (eng.class_threshold, eng.class_chunk, eng.owned_chunk) == (32, 256, 256)
+
+
+def _owned_whole_rows(eng, plans):
+    # one sum per row, and a (row, class) segment of more than one piece
+    assert bool((np.diff(plan_field(plans[0], "row_vptr")) == 1).all()) and eng.owned_chunk == 64
+    assert 64 < int(plan_field(plans[0], "seg_len").max()) <= 128
+
+
+def _owned_rest(eng, plans):
+    assert plan_field(plans[0], "row_id").size == 99 and eng.class_rows[0][0].numel() == 103
+
+
+def _owned_chunks3(overlap):
+    def more(eng, plans):
+        assert [b.row0 for b in eng.blocks] == [0, 234, 468]              # Zold + (row0 + r) * ldz, Znew + r * ldo
+        assert sum(b.nrows for b in eng.blocks) == eng.part.padded_vertices > eng.V
+        assert all(int(batches_per_group(p).max()) > 1 for p in plans)    # in every block
+        if eng.device.type == "cuda":
+            assert (eng.side_streams is not None) == overlap
+    return more
+
+
+def _owned_contiguous(eng, plans):
+    _route_contiguous(eng, eng.device)
+
+
+def _owned_tiles(widths, lanes):
+    def more(eng, plans):
+        assert [c1 - c0 for c0, c1 in eng.tiles] == widths and eng.tiles[-1][1] == eng.d == 300
+        assert lanes_per_row(max(widths), F32) == lanes and eng.owned_batch_vrows == OWNED_SUMS
+    return more
+
+
+def _route_owned_defaults(eng, dev):
+    """No setting at all: the engine chose the owned pass by itself, with the shipped constants and its own vertex
+    order; the two rows above OWNED_MAX_EDGES stay on chunk + combine."""
+    assert eng.beyond_cache and eng.class_affinity and eng.owned_possible and eng.class_owned == xcd.OWNED_DEFAULT is True
+    assert eng.hot_rows_first and not bool((eng.pos.cpu() == torch.arange(eng.V)).all())
+    assert (eng.owned_groups, eng.owned_block_threads, eng._lds_bytes, eng.owned_row_edges, eng.owned_max_edges,
+            eng.owned_loads) == (xcd.OWNED_GROUPS, xcd.OWNED_BLOCK_THREADS, xcd.OWNED_LDS_BYTES, xcd.OWNED_ROW_EDGES,
+                                 xcd.OWNED_MAX_EDGES, xcd.OWNED_LOADS) == (256, 1024, 152 * 1024, 1024, 512, 12)
+    assert len(eng.blocks) == 1 and len(eng.tiles) == 1 and len(eng.owned_rows) == 1
+    plan, rest, n_rest = eng.owned_rows[0]
+    assert rest is not None and n_rest == 2 and plan_field(plan, "n_groups") == 256
+    assert plan_field(plan, "row_id").size + n_rest == eng.class_rows[0][0].numel() == 7         # above 64 edges
+
+
+_CHUNKS3 = dict(CLASS_ON, chunks=3, hot_rows_first=False, shuffle=True, seed=SEED + 1, owned_groups=CHUNKS3_GROUPS)
+OWNED_DEFAULTS = "owned_defaults_beyond_cache"
+OWNED_PLANS = {
+    "owned_class": (own(CLASS_ON, class_phases=1), _route_owned(batches=3, steps=[8], more=_owned_class)),
+    "owned_phases2": (own(CLASS_ON, class_phases=2, phase_threshold=128), _route_owned(steps=[16], more=_owned_phases2)),
+    "owned_chunk256": (own(class_threshold=32, class_chunk=256), _route_owned(more=_owned_chunk256)),
+    "owned_whole_rows": (own(CLASS_ON, class_phases=1, owned_row_edges=1024),
+                         _route_owned(batches=3, steps=[8], more=_owned_whole_rows)),
+    "owned_rest": (own(CLASS_ON, owned_max_edges=128), _route_owned(n_rest=4, more=_owned_rest)),
+    "owned_chunks3": (own(_CHUNKS3, overlap_chunks=True), _route_owned(blocks=3, hot=False, more=_owned_chunks3(True))),
+    "owned_chunks3_in_order": (own(_CHUNKS3, overlap_chunks=False),
+                               _route_owned(blocks=3, hot=False, more=_owned_chunks3(False))),
+    "owned_contiguous": (own(CLASS_ON, table_alloc="contiguous"), _route_owned(more=_owned_contiguous)),
+    "owned_tiles2": (own(CLASS_ON, width=152, column_tiles=2), _route_owned(tiles=2, more=_owned_tiles([152, 148], 64))),
+    "owned_tiles3": (own(CLASS_ON, width=100, column_tiles=3),
+                     _route_owned(tiles=3, more=_owned_tiles([100, 100, 100], 32))),
+    OWNED_DEFAULTS: (dict(), _route_owned_defaults),
+}
+OWNED_RUNS = [(((F32, 300) if p.startswith("owned_tiles") else (F32, 128)), p) for p in OWNED_PLANS]
+
+
+def run_owned_plan(kernels, dev, case, plan, tag=None):
+    """run_plan for OWNED_PLANS; the one plan without settings is constructed as if no cache could hold the table."""
+    settings, route = OWNED_PLANS[plan]
+    tag = plan_id((case, plan)) if tag is None else tag
+    constructing = no_infinity_cache if plan == OWNED_DEFAULTS else contextlib.nullcontext
+    return run_plan(kernels, dev, engine_case(*case), settings, route, tag, constructing)
+
+
+def check_owned_plan(kernels, dev, case, plan):
+    run_owned_plan(kernels, dev, case, plan).assert_none_failed()
 
 
 # ---- B: the split route --------------------------------------------------------------------------------------------------

@@ -4,6 +4,8 @@ checking the contract the kernel relies on.  Like its base it is only ever hande
 import numpy as np
 import torch
 
+from clane_amd._hip import OWNED_MAX_STEPS
+from clane_amd.plan import lanes_per_row
 from clane_amd.xcd import xcd_class
 
 from .oracle_kernels import OracleKernels as _Base
@@ -19,6 +21,9 @@ class OracleKernels(_Base):
     def spmm_update_owned(self, colidx, P, plan, block_threads, row0, Z_old, X, gamma, Z_new, d, partials,
                           beyond_cache=False, loads=0):
         assert block_threads % 64 == 0 and 64 <= block_threads <= 1024 and plan["chunk"] % 64 == 0
+        # the kernel's instances (csrc/clane_abi.hip): 6, 8 or 12 row loads in flight at 32 lanes per row, 8 or 12 at 64
+        assert loads in (0, 8, 12) or (loads == 6 and lanes_per_row(d, Z_old.dtype) == 32), f"no instance with {loads} loads"
+        assert 1 <= plan["n_steps"] <= OWNED_MAX_STEPS
         acc, S, chunk = P.dtype, plan["n_steps"], plan["chunk"]
         gb, bv, br, bs = (plan[k] for k in ("grp_bat_ptr", "bat_vrow_ptr", "bat_row_ptr", "bat_seg_ptr"))
         assert gb.size == plan["n_groups"] + 1 and gb[-1] == bv.size - 1 and S == plan["steps"].size

@@ -3,7 +3,9 @@ the single-dropped-edge sensitivity for the sorted P order, every check of tests
 the CPU test double with the same torch.equal / == comparisons -- which proves the fixtures exact and the expectations
 right before SweepEngine ever drives a HIP kernel against them -- and mutation self-checks: a wrapping double that is
 wrong in one named way must fail the named comparison and no other (a moved table element also moves the snapshot
-distance, which is read off the same table: the two are named together)."""
+distance, which is read off the same table: the two are named together).  The double is the one with the owned class
+pass (tests/owned_oracle_kernels.py): the OWNED_PLANS run through it, and their mutations edit the plan it is handed or
+what it leaves behind."""
 import threading
 
 import numpy as np
@@ -12,7 +14,7 @@ import torch
 
 from . import engine_exact_cases as X
 from .exact_cases import BF16, F32, F64
-from .oracle_kernels import OracleKernels
+from .owned_oracle_kernels import OracleKernels          # the plain double plus spmm_update_owned
 
 DEV = "cpu"
 
@@ -89,6 +91,27 @@ def test_one_gpu_plans_on_the_double(k, run):
     X.check_plan(k, DEV, *run)
 
 
+@pytest.mark.parametrize("run", X.OWNED_RUNS, ids=X.plan_id)
+def test_owned_plans_on_the_double(k, run):
+    X.check_owned_plan(k, DEV, *run)
+
+
+def test_owned_plans_cover_what_they_are_there_for(k):
+    """What no route can see from one engine: between them the plans run 8, 16 and 32 steps, pieces of 64 and 256, sums
+    of 512 bytes and 1 KiB, segments of one edge, and launch blocks whose first row is not row 0."""
+    seen = dict(steps=set(), chunk=set(), lanes=set(), row0=set(), shortest=10 ** 9)
+    for case, plan in X.OWNED_RUNS:
+        with X.no_infinity_cache() if plan == X.OWNED_DEFAULTS else X.contextlib.nullcontext():
+            eng = X.make_engine(k, DEV, X.engine_case(*case), **X.OWNED_PLANS[plan][0])
+        for b, o in zip(eng.blocks, eng.owned_rows):
+            seen["steps"].add(o[0]["n_steps"])
+            seen["chunk"].add(o[0]["chunk"])
+            seen["row0"].add(b.row0)
+            seen["shortest"] = min(seen["shortest"], int(o[0]["seg_len"].min()))
+        seen["lanes"].add(X.lanes_per_row(max(c1 - c0 for c0, c1 in eng.tiles), F32))
+    assert seen == dict(steps={8, 16, 32}, chunk={64, 256}, lanes={32, 64}, row0={0, 234, 468}, shortest=1)
+
+
 @pytest.mark.parametrize("plan", list(X.SPLIT_PLANS))
 @pytest.mark.parametrize("case", X.SPLIT_CASES, ids=X.case_id)
 def test_split_route_on_the_double(k, case, plan):
@@ -143,6 +166,32 @@ class Mutant(OracleKernels):
                                   Z_old, X_, gamma, Z_new, d, slab, partials, **kw)
         if self.what == "class_element_moved":                         # by one quantum of the recipe
             Z_new[int(class_rows[1]), d - 1] += 0.125
+
+    def spmm_update_owned(self, colidx, P, plan, block_threads, row0, Z_old, X_, gamma, Z_new, d, partials, **kw):
+        """The owned pass, wrong in one way: through the plan it is handed, or through what it leaves behind."""
+        S, chunk = plan["n_steps"], plan["chunk"]
+        if self.what == "owned_partials_from_slot_0":                  # not after the chunk + combine rows' slots
+            plan = dict(plan, row_part=plan["row_part"] - plan["row_part"].min())
+        if self.what == "owned_last_piece_dropped":                    # of every segment of several pieces
+            ln = plan["seg_len"]
+            plan = dict(plan, seg_len=np.where(ln > chunk, (ln - 1) // chunk * chunk, ln).astype(np.int32))
+        if self.what == "owned_last_virtual_row_left_out":             # its segments never run: the sum stays zero
+            seg_bat = (np.searchsorted(plan["bat_seg_ptr"], np.arange(plan["seg_len"].size), side="right") - 1) // S
+            last = plan["row_vptr"][1:][np.diff(plan["row_vptr"]) > 1] - 1
+            keep = ~np.isin(plan["bat_vrow_ptr"][seg_bat] + plan["seg_vrow"], last)
+            kept_before = np.concatenate([[0], np.cumsum(keep)])
+            plan = dict(plan, bat_seg_ptr=kept_before[plan["bat_seg_ptr"]].astype(np.int32),
+                        **{name: plan[name][keep] for name in ("seg_e0", "seg_len", "seg_vrow")})
+        super().spmm_update_owned(colidx, P, plan, block_threads, row0, Z_old, X_, gamma, Z_new, d, partials, **kw)
+        rows = torch.from_numpy(plan["row_id"].astype(np.int64))
+        if self.what == "owned_old_row_without_row0":                  # |new - Z_old[r]| instead of |new - Z_old[row0 + r]|
+            partials[torch.from_numpy(plan["row_part"].astype(np.int64))] = \
+                (Z_new[rows, :d].double() - Z_old[rows, :d].double()).abs().sum(1)
+        if self.what == "owned_last_batch_not_stored":                 # of the first group that has several
+            gb = plan["grp_bat_ptr"]
+            b = int(gb[1:][np.diff(gb) > 1][0]) - 1
+            skipped = rows[plan["bat_row_ptr"][b]:plan["bat_row_ptr"][b + 1]]
+            Z_new[skipped, :d] = Z_old[row0 + skipped, :d]
 
     def gather_rows(self, src, idx, d, dst):
         if self.what == "halo_rows_one_sweep_late":                    # the rows as they were BEFORE this sweep
@@ -204,3 +253,62 @@ def test_mutation_l1_distance_skips_a_block():
     assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["snapshot distance"]
     sequence = X.run_sequence(Mutant("l1_skips_a_block"), DEV, X.SEQUENCE_PLANS["chunks3_class"], "l1 skips a block")
     assert sequence.failed_names() == ["snapshot distance after sweep 2"]
+
+
+# ---- mutation self-checks of the owned plans ---------------------------------------------------------------------------
+def _owned(kernels, plan):
+    case = next(c for c, p in X.OWNED_RUNS if p == plan)
+    return X.run_owned_plan(kernels, DEV, case, plan)
+
+
+@pytest.mark.parametrize("plan", ["owned_class", "owned_whole_rows", "owned_rest", "owned_chunks3", X.OWNED_DEFAULTS])
+def test_unmutated_wrapper_passes_the_owned_plans_and_every_comparison_is_made(plan):
+    checks = _owned(Mutant(None), plan)
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed == []
+
+
+def test_mutation_owned_old_row_read_without_row0():
+    """Only the delta can tell: the table is right.  Block 0 (row0 = 0) is right too, and the message says so."""
+    checks = _owned(Mutant("owned_old_row_without_row0"), "owned_chunks3")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["delta"]
+    (name, got, want, off, _, blocks), = checks.failed
+    assert [b[0] for b in blocks] == [1, 2]
+    assert _owned(Mutant("owned_old_row_without_row0"), "owned_class").failed == []         # one block: nothing to see
+
+
+def test_mutation_owned_partials_written_from_slot_0():
+    """The four rows on chunk + combine write slots 0..3 after the owned launch did: four owned rows' partials are
+    lost, and the last four slots are never written."""
+    checks = _owned(Mutant("owned_partials_from_slot_0"), "owned_rest")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["delta"]
+    assert checks.failed[0][5][0][0] == 0 and checks.failed[0][3] != 0
+    assert _owned(Mutant("owned_partials_from_slot_0"), "owned_class").failed == []     # no rows beside it: slot 0 is right
+
+
+def _rows_of_the_failed_table(checks):
+    name, _, rows = checks.failed[0]
+    assert name == "Z" and rows
+    return rows
+
+
+def test_mutation_owned_last_virtual_row_left_out():
+    checks = _owned(Mutant("owned_last_virtual_row_left_out"), "owned_class")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["Z", "delta", "snapshot distance"]
+    rows = _rows_of_the_failed_table(checks)
+    assert sorted(deg for _, deg, _ in rows) == [129, 300, 650, 700] and all(deg > 128 for _, deg, _ in rows)
+    assert _owned(Mutant("owned_last_virtual_row_left_out"), "owned_whole_rows").failed == []   # no virtual rows there
+
+
+def test_mutation_owned_last_piece_of_a_segment_dropped():
+    checks = _owned(Mutant("owned_last_piece_dropped"), "owned_whole_rows")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["Z", "delta", "snapshot distance"]
+    assert sorted(deg for _, deg, _ in _rows_of_the_failed_table(checks)) == [650, 700]     # segments of some 87 edges
+    assert _owned(Mutant("owned_last_piece_dropped"), "owned_class").failed == []           # virtual rows: one piece each
+
+
+def test_mutation_owned_last_batch_of_a_group_not_stored():
+    """Its rows keep their old values; their partials were computed from the new ones, so the delta is right."""
+    checks = _owned(Mutant("owned_last_batch_not_stored"), "owned_class")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["Z", "snapshot distance"]
+    rows = _rows_of_the_failed_table(checks)
+    assert 1 <= len(rows) <= X.OWNED_SUMS and all(deg > 32 and block == 0 for _, deg, block in rows)

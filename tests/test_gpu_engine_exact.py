@@ -34,6 +34,15 @@ def test_one_gpu_plan_exact(dev, k, run):
     X.check_plan(k, dev, *run)
 
 
+@pytest.mark.parametrize("run", X.OWNED_RUNS, ids=X.plan_id)
+def test_owned_plan_exact(dev, k, run):
+    """The same five comparisons with the class rows summed by spmm_owned_kernel: under the engine's own vertex order,
+    class rows from 33 edges, pieces of 256, whole and virtual rows, rows beside it on chunk + combine, three launch
+    blocks (row0 > 0) on side streams or in order, contiguous tables, column tiles of 152 / 148 and of 100 elements,
+    and the configuration the engine chooses by itself for a table beyond the Infinity Cache."""
+    X.check_owned_plan(k, dev, *run)
+
+
 @pytest.mark.parametrize("plan", list(X.SPLIT_PLANS))
 @pytest.mark.parametrize("case", X.SPLIT_CASES, ids=X.case_id)
 def test_split_route_exact(dev, k, case, plan):

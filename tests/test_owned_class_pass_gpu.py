@@ -1,7 +1,11 @@
 """spmm_owned_kernel on the GPU, driven by SweepEngine over the graph of tests/owned_cases.py: rows of 65..300 edges over
 all 8 classes, a row with an empty class, rows of exactly H and H + 1 edges, a segment of several pieces, rows cut into
 virtual rows, more rows than a batch holds, rows of <= 64 edges and sinks beside them.  Widths: 512-byte rows, two
-column tiles of them, ragged 1-KiB rows (d = 136: the c0 < d mask)."""
+column tiles of them, ragged 1-KiB rows (d = 136: the c0 < d mask), a ragged last pack at 32 lanes (66) and at 64 (130:
+the narrowest 64-lane width; 254: the ragged pack in lane 63), 64 full packs (256).  Every kernel instance -- 6, 8 and
+12 row loads in flight at 32 lanes per row, 8 and 12 at 64 --, the step limit, workgroups of one wave and of sixteen,
+the shipped launch configuration, batches beyond the default LDS limit and SweepEngine.set_owned.
+tests/test_owned_plan_host.py runs every case here through the CPU double first."""
 import pytest
 import torch
 
@@ -43,6 +47,15 @@ def test_integer_data_is_exact(k, dev, setting, d, tiles):
         assert int(plan.arrays["grp_bat_ptr"].diff().max()) > 1
     assert eng.sweep(1.0) == delta
     assert torch.equal(eng.get_Z(), Z1)
+    assert bool((eng.Zcur[:, d:] == 0).all())                           # the pad columns of a ragged last pack
+
+
+@pytest.mark.parametrize("run", C.LOAD_RUNS, ids=C.load_id)
+def test_integer_data_is_exact_at_every_load_count(k, dev, run):
+    """spmm_owned_kernel<4, 32, 6 | 8 | 12> and <4, 64, 8 | 12>: asked for by number, and with 0 chosen by the cache
+    hint (6 beyond the caches, else 8, at 32 lanes; 8 at 64).  accumulate_chunk walks a piece 12, 16 or 24 edges per trip
+    at 32 lanes and 8 or 12 at 64, masked by the piece's length."""
+    C.check_loads(k, dev, *run)
 
 
 @pytest.mark.parametrize("d,tiles", C.WIDTHS)
@@ -60,19 +73,33 @@ def test_gaussian_data_against_the_oracle(k, dev, setting, d, tiles):
 
 @pytest.mark.parametrize("d,tiles", C.WIDTHS)
 def test_bits_do_not_depend_on_groups_batches_workgroup_or_cache_hint(k, dev, d, tiles):
-    X, Z0, P, _, _, gamma = C.gaussian_case(d)
-    seen = None
-    for groups in (8, 16, 24):
-        for vrows in (C.BATCH_VROWS, 16):
-            for hint in (False, True):
-                eng = C.make_engine(k, dev, d, tiles, "all_phased", X, Z0, P, owned_groups=groups,
-                                    owned_lds_bytes=vrows * C.sum_bytes(d, tiles),
-                                    owned_block_threads=512 if groups == 16 else 256)
-                eng.beyond_cache = hint
-                out = (eng.sweep(gamma), eng.Zcur.clone())
-                if seen is None:
-                    seen = out
-                assert out[0] == seen[0] and torch.equal(out[1], seen[1]), (groups, vrows, hint)
+    """Nor on the row loads in flight: within a (virtual row, step, piece) the fma order is the edge order whatever U.
+    The variants: owned_cases.independence_variants -- the earlier groups x batch x hint loop, every load count, a
+    one-wave workgroup, 1024 threads."""
+    C.check_independence(k, dev, d, tiles)
+
+
+@pytest.mark.parametrize("d,threads,row_edges", C.STEPS64_RUNS)
+def test_sixty_four_steps_are_exact(k, dev, d, threads, row_edges):
+    """n_steps = 64 = kOwnedMaxSteps (8 phases x 8 classes, segments of one edge), with workgroups of 64, 256 and 1024
+    threads and with virtual rows of at most 64 edges."""
+    C.check_steps64(k, dev, d, threads, row_edges)
+
+
+@pytest.mark.parametrize("d", [128, 254])
+def test_shipped_constants_are_exact_with_most_groups_idle(k, dev, d):
+    C.check_shipped_constants(k, dev, d)
+
+
+@pytest.mark.parametrize("d", [128, 136], ids=["lanes32", "lanes64"])
+def test_the_lds_grant_grows_to_152_kib(k, dev, d):
+    """68 KiB, then 152 KiB of dynamic LDS for one kernel instance: the function attribute is raised twice."""
+    C.check_lds_grant_grows(k, dev, d)
+
+
+@pytest.mark.parametrize("d,tiles", [(128, 1), (256, 2), (130, 1)])
+def test_set_owned_replans_between_sweeps(k, dev, d, tiles):
+    C.check_set_owned(k, dev, d, tiles)
 
 
 def test_large_batches_take_the_lds_above_the_default_limit(k, dev):
@@ -101,6 +128,18 @@ def test_bad_arguments_are_refused_before_any_launch(k, dev):
     with pytest.raises(_hip.ClaneHipError):                           # no instance for narrow rows
         k.spmm_update_owned(eng.colidx, eng.P, plan, 256, 0, eng.Zcur[:, :32], eng.X_loc[:, :32], 1.0, Zn[:, :32], 32,
                             eng.partials)
+
+
+def test_load_counts_without_an_instance_are_refused_before_any_launch(k, dev):
+    """7 or 4 loads at any width, 6 at the 64-lane widths (tests/owned_oracle_kernels.py asserts the same set)."""
+    for d, loads in ((128, 7), (128, 4), (136, 6), (130, 6)):
+        X, Z0, P, _, _ = C.integer_case(d)
+        eng = C.make_engine(k, dev, d, 1, "H160", X, Z0, P)
+        Zn = torch.full_like(eng.Zcur, 7.0)
+        with pytest.raises(_hip.ClaneHipError, match=f"no instance with {loads} row loads in flight"):
+            k.spmm_update_owned(eng.colidx, eng.P, C.the_plan(eng), 256, 0, eng.Zcur, eng.X_loc, 1.0, Zn, d, eng.partials,
+                                loads=loads)
+        assert bool((Zn == 7.0).all())                                 # nothing ran
 
 
 def test_propagate_matches_the_chunk_and_combine_run(dev):

@@ -158,3 +158,47 @@ def test_owned_sweep_on_the_double_agrees_on_gaussian_data(k, d, tiles):
     (d1, za), (d0, zb) = out[True], out[False]
     assert float((za - zb).norm() / zb.norm()) < 1e-6 and d1 == pytest.approx(d0, rel=1e-6)
     assert float((za - Z1).norm() / Z1.norm()) < 2e-6 and d1 == pytest.approx(delta, rel=1e-5)
+
+
+# ---- every case of tests/test_owned_class_pass_gpu.py, first on the double ---------------------------------------------
+def test_sum_bytes_follow_the_lane_layout():
+    assert [C.lanes(d, t) for d, t in C.WIDTHS] == [32, 32, 64, 32, 64, 64, 64]
+    assert [C.sum_bytes(d, t) for d, t in C.WIDTHS] == [512, 512, 1024, 512, 1024, 1024, 1024]
+    assert [-(-d // 4) for d, _ in C.WIDTHS[3:]] == [17, 33, 64, 64] and [d % 4 for d, _ in C.WIDTHS[3:]] == [2, 2, 2, 0]
+
+
+@pytest.mark.parametrize("run", C.LOAD_RUNS, ids=C.load_id)
+def test_every_load_count_on_the_double(k, run):
+    C.check_loads(k, DEV, *run)
+
+
+def test_the_double_refuses_the_load_counts_the_kernel_refuses(k):
+    for d, loads in ((128, 7), (136, 6), (130, 6), (128, 4)):
+        eng = engine(k, "H160", d, owned_loads=loads)
+        with pytest.raises(AssertionError, match="no instance"):
+            eng.sweep(1.0)
+
+
+@pytest.mark.parametrize("d,tiles", C.WIDTHS)
+def test_bits_do_not_depend_on_the_launch_settings_on_the_double(k, d, tiles):
+    C.check_independence(k, DEV, d, tiles)
+
+
+@pytest.mark.parametrize("d,threads,row_edges", C.STEPS64_RUNS)
+def test_sixty_four_steps_on_the_double(k, d, threads, row_edges):
+    C.check_steps64(k, DEV, d, threads, row_edges)
+
+
+@pytest.mark.parametrize("d", [128, 254])
+def test_shipped_constants_on_the_double(k, d):
+    C.check_shipped_constants(k, DEV, d)
+
+
+@pytest.mark.parametrize("d", [128, 136])
+def test_batches_above_64_kib_on_the_double(k, d):
+    C.check_lds_grant_grows(k, DEV, d)
+
+
+@pytest.mark.parametrize("d,tiles", [(128, 1), (256, 2), (130, 1)])
+def test_set_owned_replans_between_sweeps_on_the_double(k, d, tiles):
+    C.check_set_owned(k, DEV, d, tiles)
