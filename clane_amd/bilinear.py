@@ -39,13 +39,13 @@ def build_P_bilinear(eng, W: torch.Tensor) -> None:
     S, N = project_table(eng, W)
     d, kern = eng.d, eng.k
     if eng.E_loc > 0:
-        for i, b in enumerate(eng.blocks):
+        for i, (b, rows) in enumerate(zip(eng.blocks, eng.block_rows)):
             rp = eng.rowptr[b.local_start:]
             kern.edge_score_pair(rp, eng.colidx, b.nrows, b.row0, S, N, d, eng.P, eng.k1_threshold,
-                                 eng.k1_long_rows[i], fuse_softmax=True)
-            if eng.class_k1 and eng.class_rows[i] is not None:
-                rows_c, slot_ptr, it_e0, it_len, it_slot, it_row, ipb = eng.class_rows[i]
-                kern.edge_score_class_pair(rp, eng.colidx, it_e0, it_len, it_slot, it_row, ipb, rows_c, slot_ptr,
-                                           b.row0, S, N, d, eng.P, eng.slabs[i % len(eng.slabs)], fuse_softmax=True,
-                                           n_slots=eng.class_slots[i], row_parts=eng.softmax_row_parts)
+                                 rows.k1_long, fuse_softmax=True)
+            if eng.class_k1 and rows.klass is not None:
+                it = rows.klass
+                kern.edge_score_class_pair(rp, eng.colidx, it.e0, it.len, it.slot, it.row, it.items_per_block, it.rows,
+                                           it.slot_ptr, b.row0, S, N, d, eng.P, eng.slabs[i % len(eng.slabs)],
+                                           fuse_softmax=True, n_slots=rows.n_slots, row_parts=eng.softmax_row_parts)
     eng.P_valid = True

@@ -83,7 +83,7 @@ class DiagnosticsMixin:
                 "class_phases": self.class_phases, "phase_threshold": self.phase_threshold,
                 "class_of_row": "xor-fold of 3-bit groups" if self.class_threshold else None,
                 "class_affinity": self.class_affinity, "mega_segment_edges": self.mega_segment_edges,
-                "class_items_per_block": [c[6] for c in self.class_rows if c is not None][:1],
+                "class_items_per_block": [c.items_per_block for c in self.class_rows if c is not None][:1],
                 "column_tiles": len(self.tiles),
                 # CLANE_SPMM_TABLE_BEYOND_CACHE changes the instances only where two fp32 rows share an instruction
                 "fewer_loads_in_flight": bool(self.beyond_cache and self.d > 0 and (str(self.dtype), lanes_per_row(

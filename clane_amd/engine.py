@@ -24,6 +24,7 @@ the column split (the default division) that scalar is the only p
 from __future__ import annotations
 
 import contextlib
+import itertools
 import threading
 from typing import List, Optional
 
@@ -31,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _hip, owned, xcd
+from .blocks import BlockRows, ClassItems, PartialLayout, SplitRows
 from .comm import TorchComm
 from .diagnostics import DiagnosticsMixin
 from .halo import build_halo_layout
@@ -340,25 +342,14 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         return deg
 
     def _bin_rows(self, deg: np.ndarray, split_hubs: bool) -> None:
-        """Per launch block: the row lists of each kernel (relative to the block's first row: the kernels get rowptr / X /
-        Z_new offset to it), the class items, the slots of the fixed-order delta partials, the slabs."""
+        """Per launch block, one BlockRows (blocks.py): the row lists of each kernel, the class items, the owned plan,
+        the layout of the fixed-order delta partials; then the partials and the slabs."""
         dev = self.device
-        self.long_rows: List[Optional[torch.Tensor]] = []     # every row above score_threshold (K1 / K2 slice these)
-        self.mid_rows: List[Optional[torch.Tensor]] = []      # long_threshold < deg <= hub_threshold: 4 waves/row
-        self.hub_rows: List[Optional[torch.Tensor]] = []      # hub_threshold < deg <= SPLIT_EDGES: 16 waves/row
-        self.split_rows: List[Optional[tuple]] = []           # deg > SPLIT_EDGES: (rows, seg_ptr, seg_row) on device
-        self.class_rows: List[Optional[tuple]] = []           # deg > class_threshold: (rows, slot_ptr, e0, len, slot, row)
-        self.class_slots: List[int] = []                      # slot_ptr[-1] of each block's class rows, known on the host
-        # class_owned: per block (plan of the owned rows, launch lists of the class rows above owned_max_edges or None,
-        # number of those rows); the delta partials of a block's class rows are then [rows above, owned rows]
-        self.owned_rows: List[Optional[tuple]] = []
-        self._owned_inputs = {}
-        self.k1_long_rows: List[Optional[torch.Tensor]] = []  # K1's workgroup-per-row list: above k1_threshold, not class
+        self.block_rows: List[BlockRows] = []
         self.split_edges = SPLIT_EDGES if split_hubs else 0
         hub_edges = int(deg[deg > SPLIT_EDGES].sum()) // max(1, len(self.blocks))
         self.segment_edges = int(min(SPLIT_EDGES, max(MIN_SEGMENT_EDGES, hub_edges // TARGET_SEGMENTS // 1024 * 1024)))
         max_segments = max_slots = 0
-        self.partial_off = [0]
         to_dev = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev) if a.size else None  # noqa: E731
         for b in self.blocks:
             db = deg[b.local_start:b.local_start + b.nrows]
@@ -367,10 +358,17 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
             is_long = is_long | is_class
             is_split = (is_long & (db > self.split_edges) if self.split_edges > 0 else np.zeros_like(is_long)) & ~is_class
             is_hub = is_long & (db > self.hub_threshold) & ~is_split & ~is_class
-            self.long_rows.append(to_dev(np.nonzero(db > self.score_threshold)[0] if self.score_threshold > 0
-                                         else np.empty(0, dtype=np.int64)))
-            self.mid_rows.append(to_dev(np.nonzero(is_long & ~is_hub & ~is_split & ~is_class)[0]))
-            rows_c = np.nonzero(is_class)[0]
+            is_mid = is_long & ~is_hub & ~is_split & ~is_class
+            k1_long = (db > self.k1_threshold) & ~(is_class if self.class_k1 else np.zeros_like(is_class)) \
+                if self.k1_threshold > 0 else np.zeros_like(is_class)
+            rows_c, rows_s = np.nonzero(is_class)[0], np.nonzero(is_split)[0]
+            layout = PartialLayout.of(row_pass=self.k.spmm_partials_len(b.nrows, 0), n_mid=int(is_mid.sum()),
+                                      n_hub=int(is_hub.sum()), n_split=rows_s.size, n_class=rows_c.size,
+                                      length=self.k.spmm_partials_len(b.nrows, int(is_long.sum())))
+            rows = BlockRows(long=to_dev(np.nonzero(db > self.score_threshold)[0] if self.score_threshold > 0
+                                         else np.empty(0, dtype=np.int64)),
+                             k1_long=to_dev(np.nonzero(k1_long)[0]), mid=to_dev(np.nonzero(is_mid)[0]),
+                             hub=to_dev(np.nonzero(is_hub)[0]), partials=layout)
             if rows_c.size:
                 rows_abs = rows_c + b.local_start
                 phased = dict(phase_threshold=self.phase_threshold, phases=self.class_phases,
@@ -382,36 +380,20 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                                             self.phase_threshold, self.class_phases)
                 items = class_items(self.local.rowptr, self.local.colidx, rows_abs, self.class_chunk, None,
                                     row_ids=rows_c, colidx_dev=self.colidx, segments=segments, **phased)
-                self.owned_rows.append(owned.plan_block(self, rows_c, rows_abs, segments, phased) if self.class_owned else None)
                 if self.owned_possible:             # set_owned() plans from these again
-                    self._owned_inputs[len(self.owned_rows) - 1] = (rows_c, rows_abs, segments, phased)
-                ipb = items["items_per_block"]
-                self.class_rows.append((to_dev(rows_c), torch.from_numpy(items["slot_ptr"]).to(dev),
-                                        torch.from_numpy(items["e0"]).to(dev), torch.from_numpy(items["len"]).to(dev),
-                                        torch.from_numpy(items["slot"]).to(dev), torch.from_numpy(items["row"]).to(dev),
-                                        ipb))
-                self.class_slots.append(int(items["slot_ptr"][-1]))
-                max_slots = max(max_slots, self.class_slots[-1])
-            else:
-                self.class_rows.append(None)
-                self.class_slots.append(0)
-                self.owned_rows.append(None)
-            k1_long = (db > self.k1_threshold) & ~(is_class if self.class_k1 else np.zeros_like(is_class)) \
-                if self.k1_threshold > 0 else np.zeros_like(is_class)
-            self.k1_long_rows.append(to_dev(np.nonzero(k1_long)[0]))
-            self.hub_rows.append(to_dev(np.nonzero(is_hub)[0]))
-            rows_s = np.nonzero(is_split)[0]
+                    rows.owned_inputs = (rows_c, rows_abs, segments, phased)
+                if self.class_owned:
+                    rows.owned = owned.plan_block(self, layout, *rows.owned_inputs)
+                rows.klass, rows.n_slots = ClassItems.upload(items, rows_c, dev), int(items["slot_ptr"][-1])
+                max_slots = max(max_slots, rows.n_slots)
             if rows_s.size:
                 nseg = -(-db[rows_s] // self.segment_edges)
                 seg_ptr = np.zeros(rows_s.size + 1, dtype=np.int64)
                 np.cumsum(nseg, out=seg_ptr[1:])
                 seg_row = np.repeat(np.arange(rows_s.size, dtype=np.int32), nseg)
-                self.split_rows.append((to_dev(rows_s), torch.from_numpy(seg_ptr).to(dev),
-                                        torch.from_numpy(seg_row).to(dev)))
+                rows.split = SplitRows(to_dev(rows_s), torch.from_numpy(seg_ptr).to(dev), torch.from_numpy(seg_row).to(dev))
                 max_segments = max(max_segments, int(seg_ptr[-1]))
-            else:
-                self.split_rows.append(None)
-            self.partial_off.append(self.partial_off[-1] + self.k.spmm_partials_len(b.nrows, int(is_long.sum())))
+            self.block_rows.append(rows)
         # one set of fixed-order delta partials per column tile, summed together by the sweep's final reduction
         self.partials = torch.zeros(self.partial_off[-1] * len(self.tiles), dtype=torch.float64, device=dev)
         # segment sums of the split hub rows: one slab per launch stream (blocks on a stream run in order)
@@ -421,6 +403,20 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         # one slab per launch stream: blocks alternate between two side streams when there are several
         self.slabs = [torch.zeros(slab_len, dtype=self.acc_dtype, device=dev)
                       for _ in range(2 if len(self.blocks) > 1 else 1)]
+
+    # the per-block lists other modules, the tools and the tests read: views of block_rows, entry i of block i
+    def _per_block(name):                                                                  # noqa: N805
+        return property(lambda self: [getattr(r, name) for r in self.block_rows])
+
+    long_rows, k1_long_rows = _per_block("long"), _per_block("k1_long")
+    mid_rows, hub_rows, split_rows = _per_block("mid"), _per_block("hub"), _per_block("split")
+    class_rows, class_slots, owned_rows = _per_block("klass"), _per_block("n_slots"), _per_block("owned")
+    del _per_block
+
+    @property
+    def partial_off(self) -> List[int]:
+        """First delta slot of every block within a column tile's partials, and their total."""
+        return list(itertools.accumulate((r.partials.end for r in self.block_rows), initial=0))
 
     def set_owned(self, on: bool, **settings) -> None:
         """Switch the owned pass on or off between sweeps, or plan it again with other settings (``max_edges``,
@@ -440,8 +436,8 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self.class_owned = bool(on)
         if on:
             self._check_owned_settings()
-        self.owned_rows = [owned.plan_block(self, *self._owned_inputs[i]) if on and i in self._owned_inputs else None
-                           for i in range(len(self.blocks))]
+        for r in self.block_rows:         # r.partials stays: both halves fill its class region (owned_slots asserts it)
+            r.owned = owned.plan_block(self, r.partials, *r.owned_inputs) if on and r.owned_inputs is not None else None
         self._plans = {}
 
     def _setup_exchange(self, deg: np.ndarray, fused_pack: bool) -> None:
@@ -727,36 +723,36 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 self._all_reduce(self.sq_full)                    # partial norms over the ranks' column slices
             sq = self.sq_full
         if self.E_loc > 0 and not self.columns:
-            for i, b in enumerate(self.blocks):
+            for i, (b, rows) in enumerate(zip(self.blocks, self.block_rows)):
                 rp = self.rowptr[b.local_start:]
                 # K1 soft-maxes every row it scores: one wave in registers / online, a listed row by its workgroup
                 k.edge_score(rp, self.colidx, b.nrows, b.row0, Z, self.d, mode, self.sums2, sq, self.P,
-                             self.k1_threshold, self.k1_long_rows[i], fuse_softmax=True)
-                if self.class_k1 and self.class_rows[i] is not None:
-                    rows_c, slot_ptr, it_e0, it_len, it_slot, it_row, ipb = self.class_rows[i]
-                    k.edge_score_class(rp, self.colidx, it_e0, it_len, it_slot, it_row, ipb, rows_c,
-                                       slot_ptr, b.row0, Z, self.d, mode, self.sums2, sq, self.P,
+                             self.k1_threshold, rows.k1_long, fuse_softmax=True)
+                if self.class_k1 and rows.klass is not None:
+                    it = rows.klass
+                    k.edge_score_class(rp, self.colidx, it.e0, it.len, it.slot, it.row, it.items_per_block, it.rows,
+                                       it.slot_ptr, b.row0, Z, self.d, mode, self.sums2, sq, self.P,
                                        self.slabs[i % len(self.slabs)], fuse_softmax=True,
-                                       n_slots=self.class_slots[i], row_parts=self.softmax_row_parts)
+                                       n_slots=rows.n_slots, row_parts=self.softmax_row_parts)
         elif self.E_loc > 0:
             # column split: dot products of the owned columns, summed over the ranks, then denominators + softmax
             if busy:
-                for i, b in enumerate(self.blocks):
+                for b, rows in zip(self.blocks, self.block_rows):
                     k.edge_score(self.rowptr[b.local_start:], self.colidx, b.nrows, b.row0, Z, self.d,
-                                 _hip.SCORE_RAW_DOT, None, None, self.P, self.k1_threshold, self.k1_long_rows[i])
-                    if self.class_k1 and self.class_rows[i] is not None:
-                        rows_c, slot_ptr, it_e0, it_len, it_slot, it_row, ipb = self.class_rows[i]
-                        k.edge_score_class(self.rowptr[b.local_start:], self.colidx, it_e0, it_len, it_slot, it_row,
-                                           ipb, rows_c, slot_ptr, b.row0, Z, self.d,
+                                 _hip.SCORE_RAW_DOT, None, None, self.P, self.k1_threshold, rows.k1_long)
+                    if self.class_k1 and rows.klass is not None:
+                        it = rows.klass
+                        k.edge_score_class(self.rowptr[b.local_start:], self.colidx, it.e0, it.len, it.slot, it.row,
+                                           it.items_per_block, it.rows, it.slot_ptr, b.row0, Z, self.d,
                                            _hip.SCORE_RAW_DOT, None, None, self.P)
             else:
                 self.P.zero_()
             self._all_reduce(self.P)                              # every rank holds the same rows, other columns
-            for i, b in enumerate(self.blocks):
+            for b, rows in zip(self.blocks, self.block_rows):
                 rp = self.rowptr[b.local_start:]
                 k.edge_score_finalize(rp, self.colidx, b.nrows, b.row0, mode, self.sums2, sq, self.P)
-                k.segment_softmax(rp, b.nrows, self.P, 0, self.score_threshold if self.long_rows[i] is not None else 0,
-                                  self.long_rows[i])
+                k.segment_softmax(rp, b.nrows, self.P, 0, self.score_threshold if rows.long is not None else 0,
+                                  rows.long)
         self.P_valid = True
 
     def build_P_bilinear(self, W: torch.Tensor) -> None:
@@ -804,20 +800,16 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         marks and the exchange; then the final reduction (into delta slot `tick`).  Everything that can be computed once (views, pointers, offsets,
         the stream each call goes to) is, so the per-sweep host cost is a few microseconds per launch -- it
         matters at 8 GPUs, where a sweep is ~1 ms of GPU time."""
-        k = self.k
         Zold, Znew = self.Zbuf[cur], self.Zbuf[dst]
         per_block = []
-        for i, b in enumerate(self.blocks):
+        partial_off = self.partial_off
+        for i, (b, rows) in enumerate(zip(self.blocks, self.block_rows)):
             steps = []
             ctx = torch.cuda.stream(self.side_streams[i % 2]) if self.side_streams else contextlib.nullcontext()
             with ctx:            # bound calls capture the current stream
                 rp, Xb, Zn = self.rowptr[b.local_start:], self.X_loc[self._rows(b)], self._zrows(Znew, b)
-                po = self.partial_off[i]
+                po, lay = partial_off[i], rows.partials
                 mir = self.mirrors_p2p[dst][i] if self.p2p else self.mirrors[i]
-                po_mid = po + k.spmm_partials_len(b.nrows, 0)
-                po_hub = po_mid + (0 if self.mid_rows[i] is None else self.mid_rows[i].numel())
-                po_split = po_hub + (0 if self.hub_rows[i] is None else self.hub_rows[i].numel())
-                po_class = po_split + (0 if self.split_rows[i] is None else self.split_rows[i][0].numel())
                 # biggest rows first: split hubs, 16-wave rows, (4-wave rows), then the one-(sub-)wave-per-row pass
                 steps.append(("event", i, 0))
                 if self.d == 0:              # column-split rank without columns: nothing to launch, delta stays 0
@@ -827,50 +819,46 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 T = len(self.tiles)
                 cut = (lambda M, t: M) if T == 1 else (lambda M, t: M[:, self.tiles[t][0]:self.tiles[t][1]])
                 width = (lambda t: self.d) if T == 1 else (lambda t: self.tiles[t][1] - self.tiles[t][0])
-                part = lambda off, t: self.partials[t * self.partial_off[-1] + off:]      # noqa: E731
+                # the block's delta partials of tile t from a start of its layout (blocks.PartialLayout) on
+                part = lambda start, t: self.partials[t * partial_off[-1] + po + start:]      # noqa: E731
                 if mir is not None and T > 1:
                     raise AssertionError("column tiles and mirrored launches do not combine")
+
+                def class_launch(items, t):         # chunk + combine over `items` (a ClassItems) of this block
+                    return ("call", self._bind("spmm_update_class", self.colidx, self.P, items.e0, items.len, items.slot,
+                                               items.items_per_block, items.rows, items.slot_ptr, b.row0, cut(Zold, t),
+                                               cut(Xb, t), gamma, cut(Zn, t), width(t), self.slabs[i % len(self.slabs)],
+                                               part(lay.klass, t), mirror=mir, beyond_cache=self.beyond_cache))
                 for t in range(T):
-                    if self.owned_rows[i] is not None:      # the owned rows in LDS, the rows above them by chunk + combine
-                        plan, rest, _ = self.owned_rows[i]
-                        steps.append(("call", owned.bind_launch(self, plan, b.row0, cut(Zold, t), cut(Xb, t), gamma,
-                                                                cut(Zn, t), width(t), part(po_class, t))))
-                        if rest is not None:
-                            rows_r, slot_ptr, it_e0, it_len, it_slot, ipb = rest
-                            steps.append(("call", self._bind("spmm_update_class", self.colidx, self.P, it_e0, it_len,
-                                                             it_slot, ipb, rows_r, slot_ptr, b.row0, cut(Zold, t),
-                                                             cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                             self.slabs[i % len(self.slabs)], part(po_class, t),
-                                                             mirror=mir, beyond_cache=self.beyond_cache)))
-                    elif self.class_rows[i] is not None:
-                        rows_c, slot_ptr, it_e0, it_len, it_slot, _, ipb = self.class_rows[i]
-                        steps.append(("call", self._bind("spmm_update_class", self.colidx, self.P, it_e0, it_len, it_slot,
-                                                         ipb, rows_c, slot_ptr, b.row0, cut(Zold, t), cut(Xb, t), gamma,
-                                                         cut(Zn, t), width(t), self.slabs[i % len(self.slabs)],
-                                                         part(po_class, t), mirror=mir, beyond_cache=self.beyond_cache)))
-                    if self.split_rows[i] is not None:
-                        rows_s, seg_ptr, seg_row = self.split_rows[i]
-                        steps.append(("call", self._bind("spmm_update_split", rp, self.colidx, self.P, rows_s, seg_ptr,
-                                                         seg_row, self.segment_edges, b.row0, cut(Zold, t), cut(Xb, t), gamma,
-                                                         cut(Zn, t), width(t), self.slabs[i % len(self.slabs)],
-                                                         part(po_split, t), mirror=mir)))
+                    if rows.owned is not None:      # the owned rows in LDS, the rows above them by chunk + combine
+                        steps.append(("call", owned.bind_launch(self, rows.owned.plan, b.row0, cut(Zold, t), cut(Xb, t),
+                                                                gamma, cut(Zn, t), width(t), part(lay.klass, t))))
+                        if rows.owned.rest is not None:
+                            steps.append(class_launch(rows.owned.rest, t))
+                    elif rows.klass is not None:
+                        steps.append(class_launch(rows.klass, t))
+                    if rows.split is not None:
+                        steps.append(("call", self._bind("spmm_update_split", rp, self.colidx, self.P, rows.split.rows,
+                                                         rows.split.seg_ptr, rows.split.seg_row, self.segment_edges, b.row0,
+                                                         cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
+                                                         self.slabs[i % len(self.slabs)], part(lay.split, t), mirror=mir)))
                 steps.append(("event", i, 4))
                 for t in range(T):
-                    if self.hub_rows[i] is not None:
-                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, self.hub_rows[i], 16,
+                    if rows.hub is not None:
+                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, rows.hub, 16,
                                                          b.row0, cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                         part(po_hub, t), mirror=mir)))
+                                                         part(lay.hub, t), mirror=mir)))
                 steps.append(("event", i, 1))
                 for t in range(T):
-                    if self.mid_rows[i] is not None:
-                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, self.mid_rows[i], 4,
+                    if rows.mid is not None:
+                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, rows.mid, 4,
                                                          b.row0, cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                         part(po_mid, t), mirror=mir)))
+                                                         part(lay.mid, t), mirror=mir)))
                 steps.append(("event", i, 2))
                 for t in range(T):
                     steps.append(("call", self._bind("spmm_update", rp, self.colidx, self.P, b.nrows, b.row0, cut(Zold, t),
                                                      cut(Xb, t), gamma, cut(Zn, t), width(t), self.long_threshold,
-                                                     part(po, t), sinks_untouched=True, mirror=mir,
+                                                     part(lay.main, t), sinks_untouched=True, mirror=mir,
                                                      beyond_cache=self.beyond_cache)))
                 steps.append(("event", i, 3))
                 if b.span is not None:

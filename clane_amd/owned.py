@@ -7,9 +7,9 @@ from __future__ import annotations
 from typing import Optional
 
 import numpy as np
-import torch
 
 from . import xcd
+from .blocks import ClassItems, OwnedRows, PartialLayout
 
 
 def possible(eng) -> bool:
@@ -19,10 +19,11 @@ def possible(eng) -> bool:
                 and all(eng.k.has_spmm_owned(eng.dtype, w) for w in widths))
 
 
-def plan_block(eng, rows_c: np.ndarray, rows_abs: np.ndarray, segments, phased: dict) -> Optional[tuple]:
-    """One block's class rows divided between the owned pass (at most owned_max_edges edges) and chunk + combine:
-    (plan on the device, launch lists of the rows above or None, number of rows above); None without owned rows.  The
-    delta partials of the block's class rows are then [rows above, owned rows]."""
+def plan_block(eng, layout: PartialLayout, rows_c: np.ndarray, rows_abs: np.ndarray, segments,
+               phased: dict) -> Optional[OwnedRows]:
+    """One block's class rows divided between the owned pass (at most owned_max_edges edges) and chunk + combine: the
+    plan on the device, the class items of the rows above or None, the number of rows above; None without owned rows.
+    `layout` says which of the block's delta partials the owned rows get."""
     dev = eng.device
     sizes, seg_len, seg_e0 = segments
     NS = seg_len.size // max(1, sizes.size)
@@ -32,7 +33,7 @@ def plan_block(eng, rows_c: np.ndarray, rows_abs: np.ndarray, segments, phased: 
     n_rest = int((~own).sum())
     pick = lambda a, m: a.reshape(sizes.size, NS)[m].reshape(-1)       # noqa: E731
     plan = xcd.owned_plan(sizes[own], pick(seg_len, own), pick(seg_e0, own), rows_c[own],
-                          n_rest + np.arange(int(own.sum())), row_edges=eng.owned_row_edges,
+                          layout.owned_slots(n_rest, int(own.sum())), row_edges=eng.owned_row_edges,
                           groups=eng.owned_groups, batch_vrows=eng.owned_batch_vrows)
     eng.owned_balance = plan["group_step_edges"]
     rest = None
@@ -41,10 +42,8 @@ def plan_block(eng, rows_c: np.ndarray, rows_abs: np.ndarray, segments, phased: 
         items = xcd.class_items(eng.local.rowptr, eng.local.colidx, rows_abs[keep], eng.class_chunk, None,
                                 row_ids=rows_c[keep], segments=(sizes[keep], pick(seg_len, keep), pick(seg_e0, keep)),
                                 **phased)
-        rest = (torch.from_numpy(rows_c[keep].astype(np.int32)).to(dev), torch.from_numpy(items["slot_ptr"]).to(dev),
-                torch.from_numpy(items["e0"]).to(dev), torch.from_numpy(items["len"]).to(dev),
-                torch.from_numpy(items["slot"]).to(dev), items["items_per_block"])
-    return eng.k.make_owned_plan(plan, eng.owned_chunk, dev), rest, n_rest
+        rest = ClassItems.upload(items, rows_c[keep], dev)
+    return OwnedRows(eng.k.make_owned_plan(plan, eng.owned_chunk, dev), rest, n_rest)
 
 
 def bind_launch(eng, plan, row0: int, Zold, Xb, gamma: float, Zn, width: int, partials):

@@ -6,6 +6,9 @@ wrong in one named way must fail the named comparison and no other (a moved tabl
 distance, which is read off the same table: the two are named together).  The double is the one with the owned class
 pass (tests/owned_oracle_kernels.py): the OWNED_PLANS run through it, and their mutations edit the plan it is handed or
 what it leaves behind."""
+import dataclasses
+import functools
+import inspect
 import threading
 
 import numpy as np
@@ -253,6 +256,118 @@ def test_mutation_l1_distance_skips_a_block():
     assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["snapshot distance"]
     sequence = X.run_sequence(Mutant("l1_skips_a_block"), DEV, X.SEQUENCE_PLANS["chunks3_class"], "l1 skips a block")
     assert sequence.failed_names() == ["snapshot distance after sweep 2"]
+
+
+# ---- every delta slot is written by exactly one launch -----------------------------------------------------------------
+class SlotRecorder(OracleKernels):
+    """The double with every K3 call of a sweep replaced by a note of the block's first row and the delta slots the
+    call is to write: from the storage offset of its `partials` view on, the row pass' grid length, one per listed
+    row, or the plan's row_part.  (What the calls compute is the other tests' matter.)"""
+
+    def __init__(self):
+        self.writes = []                                               # (method, row0, slots of eng.partials)
+
+    def bind(self, method, *args, **kwargs):
+        if not method.startswith("spmm_update"):
+            return super().bind(method, *args, **kwargs)
+        a = inspect.signature(getattr(self, method)).bind(*args, **kwargs).arguments
+        if method == "spmm_update":
+            slots = np.arange(self.spmm_partials_len(a["nrows"], 0))
+        elif method == "spmm_update_owned":
+            slots = np.asarray(a["plan"]["row_part"], dtype=np.int64)
+        else:
+            slots = np.arange(next(a[n] for n in ("long_rows", "split_rows", "class_rows") if n in a).numel())
+        write = (method, a["row0"], a["partials"].storage_offset() + slots)
+        return lambda: self.writes.append(write)
+
+
+def delta_slot_faults(eng, writes):
+    """What is wrong with the slots the K3 calls of ONE sweep wrote; [] when they are pairwise disjoint, cover every
+    column tile's [0, partial_off[-1]) exactly and stay inside their block's [partial_off[i], partial_off[i + 1])."""
+    off, faults = eng.partial_off, []
+    block = {b.row0: i for i, b in enumerate(eng.blocks)}
+    for method, row0, slots in writes:
+        i, within = block[row0], slots % off[-1]
+        if slots.size and not (off[i] <= within.min() and within.max() < off[i + 1]):
+            faults.append(f"{method} of block {i} leaves [{off[i]}, {off[i + 1]}): {within.min()}..{within.max()}")
+    every = np.concatenate([slots for _, _, slots in writes])
+    if np.unique(every).size != every.size:
+        faults.append(f"{every.size - np.unique(every).size} slots are written twice")
+    if not np.array_equal(np.sort(every), np.arange(len(eng.tiles) * off[-1])):
+        faults.append(f"{np.unique(every).size} of {len(eng.tiles) * off[-1]} slots are written")
+    return faults
+
+
+@functools.lru_cache(maxsize=None)
+def _slot_engine(run, before_sweep=None):
+    """The engine of one (case, plan) over a SlotRecorder after one sweep, and the recorder's writes.  Made once per
+    run; nobody sweeps it again."""
+    kind, case, plan = run
+    settings = {"plan": X.PLANS, "owned": X.OWNED_PLANS, "split": X.SPLIT_PLANS}[kind][plan][0]
+    c = X.engine_case(case[0], case[1], "split" if kind == "split" else "ragged")
+    rec = SlotRecorder()
+    with X.no_infinity_cache() if plan == X.OWNED_DEFAULTS else X.contextlib.nullcontext():
+        eng = X.make_engine(rec, DEV, c, **settings)
+    if before_sweep is not None:
+        before_sweep(eng)
+    eng.sweep(X.GAMMA)
+    return eng, rec.writes
+
+
+# every plan once: the one-GPU plans on the first case they are run at, the owned plans, the split plans
+SLOT_RUNS = ([("plan", next(c for c, q in X.PLAN_RUNS if q == p and (not p.startswith("tiles") or c[1] == 300)), p)
+              for p in X.PLANS] + [("owned", c, p) for c, p in X.OWNED_RUNS]
+             + [("split", X.SPLIT_CASES[0], p) for p in X.SPLIT_PLANS])
+
+
+@pytest.mark.parametrize("run", SLOT_RUNS, ids=lambda run: f"{run[0]}-{X.plan_id(run[1:])}")
+def test_every_delta_slot_is_written_by_exactly_one_launch(run):
+    """The layout of a block's delta partials (blocks.PartialLayout) against what the launches do with it: two
+    launches sharing slots, or a slot nobody writes, change the delta by a few rows' worth -- nothing a convergence
+    loop would notice."""
+    eng, writes = _slot_engine(run)
+    methods = {m for m, _, _ in writes}
+    assert "spmm_update" in methods and len(writes) >= len(eng.blocks) * len(eng.tiles)
+    assert ("spmm_update_owned" in methods) == (run[0] == "owned")
+    assert delta_slot_faults(eng, writes) == []
+
+
+def test_slot_runs_reach_every_bin_and_division():
+    """Between them: every K3 kernel, both widths of the long-row kernel in one block, several blocks, several
+    tiles, owned rows with and without rows beside them."""
+    seen = dict(methods=set(), blocks=set(), tiles=set(), owned=set(), both_long=False)
+    for run in SLOT_RUNS:
+        eng, writes = _slot_engine(run)
+        seen["methods"] |= {m for m, _, _ in writes}
+        seen["blocks"].add(len(eng.blocks))
+        seen["tiles"].add(len(eng.tiles))
+        seen["owned"] |= {o.rest is not None for o in eng.owned_rows if o is not None}
+        seen["both_long"] |= any(r.mid is not None and r.hub is not None for r in eng.block_rows)
+    assert seen == dict(methods={"spmm_update", "spmm_update_long", "spmm_update_split", "spmm_update_class",
+                                 "spmm_update_owned"}, blocks={1, 3}, tiles={1, 2, 3}, owned={False, True}, both_long=True)
+
+
+def test_mutation_layout_puts_the_16_wave_rows_on_the_4_wave_rows_slots():
+    """A PartialLayout whose `hub` start is its `mid` start: the slot check names it, and of the exact comparisons
+    the delta -- the 4-wave launch overwrites what the 16-wave rows left -- and nothing else."""
+    def mutate(eng):
+        for r in eng.block_rows:
+            r.partials = dataclasses.replace(r.partials, hub=r.partials.mid)
+
+    run = ("plan", (F32, 128), "bins_4_and_16_waves")
+    eng, writes = _slot_engine(run, mutate)
+    faults = delta_slot_faults(eng, writes)
+    n_hub, n = eng.hub_rows[0].numel(), eng.partial_off[-1]
+    assert 0 < n_hub <= eng.mid_rows[0].numel()
+    assert faults == [f"{n_hub} slots are written twice", f"{n - n_hub} of {n} slots are written"]
+    assert delta_slot_faults(*_slot_engine(run)) == []
+
+    def route(eng, dev):
+        X.PLANS[run[2]][1](eng, dev)
+        mutate(eng)
+    checks = X.run_plan(OracleKernels(), DEV, X.engine_case(*run[1]), X.PLANS[run[2]][0], route, "hub on mid")
+    assert checks.names == ONE_SWEEP_NAMES and checks.failed_names() == ["delta"]
+    assert checks.failed[0][3] < 0 and checks.failed[0][5][0][0] == 0          # short, and block 0 is named
 
 
 # ---- mutation self-checks of the owned plans ---------------------------------------------------------------------------
