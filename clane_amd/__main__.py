@@ -84,13 +84,21 @@ def embedding(args):
             raise ValueError("node_clustering: the section needs 'labels', the file of id<TAB>class lines, or 'clusters', "
                              "the number of clusters")
     # optional section (extension): content_reduction: {dim: 128, center: true, whiten: false, load: pca.npz} -- the
-    # content's principal components instead of the content (reduce.py); checked before the graph loads
+    # content's principal components instead of the content (reduce.py); checked before the graph loads.  With
+    # sparse: C.npz (and oversample / power_iterations / seed) the content is a CSR bag of words, read and validated here
     reduction = hparams.get("content_reduction") if isinstance(hparams, dict) else None
-    reduction_file = None
+    reduction_file = sparse_content = None
     if reduction is not None:
         from . import reduce
         reduction = reduce.check_section(reduction, int(os.environ.get("WORLD_SIZE", "1")))
         reduction_file = reduce.resolve_load(reduction, Path(args.data_root))
+        sparse_content = reduce.resolve_sparse(reduction, Path(args.data_root))
+        if sparse_content is not None:
+            from .graph import read_vertex_ids
+            n_vertices = len(read_vertex_ids(Path(args.data_root)))
+            if sparse_content.shape[0] != n_vertices:
+                raise ValueError(f"content_reduction: sparse: the file holds {sparse_content.shape[0]} rows, V lists "
+                                 f"{n_vertices} vertices")
     # optional section (extension): new_vertices: {root: arrivals, max_rounds: 64, weights: true} -- vertices that are not
     # in V, embedded against the finished graph (induct.py); everything about the files is checked before the graph loads
     new_vertices = hparams.get("new_vertices") if isinstance(hparams, dict) else None
@@ -112,7 +120,7 @@ def embedding(args):
     g = Graph(data_root=args.data_root, **hparams["graph"])
     if reduction is not None:                       # before the banner: its statistics are the reduced content's
         from .reduce import ContentPCA
-        original_width = int(g.X.shape[1])
+        original_width = int(g.X.shape[1]) if sparse_content is None else int(sparse_content.shape[1])
         if arrivals is not None and arrivals[1].shape[1] != original_width:
             raise ValueError(f"new_vertices: with content_reduction the arrivals' content must have the graph's ORIGINAL "
                              f"width {original_width} (it is reduced to {reduction['dim'] or 'the loaded width'} by the "
@@ -125,7 +133,14 @@ def embedding(args):
             if loaded.components_.shape[1] != original_width:
                 raise ValueError(f"content_reduction: {str(reduction_file)!r} was fitted on {loaded.components_.shape[1]} "
                                  f"columns, the content has {original_width}")
-            g.reduce_content(loaded.dim, transform=loaded)
+            if sparse_content is not None:
+                g.reduce_sparse_content(sparse_content, loaded.dim, transform=loaded)
+            else:
+                g.reduce_content(loaded.dim, transform=loaded)
+        elif sparse_content is not None:
+            g.reduce_sparse_content(sparse_content, reduction["dim"], center=reduction["center"],
+                                    whiten=reduction["whiten"], oversample=reduction["oversample"],
+                                    power_iterations=reduction["power_iterations"], seed=reduction["seed"])
         else:
             g.reduce_content(reduction["dim"], center=reduction["center"], whiten=reduction["whiten"])
         if arrivals is not None:                    # the graph's mean and components, never a re-fit
@@ -142,7 +157,12 @@ def embedding(args):
     say("Graph Loaded.")
     say(f" - {len(g)} vertices")
     say(f" - {len(g.E)} edges")
-    if reduction is not None:
+    if reduction is not None and g.content_transform.sparse_fit_ is not None:
+        fit = g.content_transform.sparse_fit_
+        say(f" - Content Embeddings (reduced from {original_width} sparse columns, {fit['nnz']} non-zeros; method: "
+            f"randomized, oversample {fit['oversample']}, power_iterations {fit['power_iterations']}, seed {fit['seed']}; "
+            f"{g.content_transform.explained_variance_ratio_.sum():.3f} of the variance kept):")
+    elif reduction is not None:
         say(f" - Content Embeddings (reduced from {original_width} columns; "
             f"{g.content_transform.explained_variance_ratio_.sum():.3f} of the variance kept):")
     else:

@@ -129,6 +129,12 @@ for _s in ("f32", "f64", "bf16"):   # content reduction (csrc/content_pca.h)
     SIGNATURES[f"clane_project_affine_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _i32, _p, _i64, _p])
 SIGNATURES["clane_column_sums_ws_len"] = (_i64, [_i64, _i32])
 SIGNATURES["clane_gram_ws_len"] = (_i64, [_i64, _i32])
+CSR_MAX_L = 512                     # CLANE_CSR_MAX_L; sparse content (csrc/sparse_rows.h)
+SIGNATURES["clane_csr_spmm_segment"] = (C.c_int, [])
+SIGNATURES["clane_csr_spmm_ws_len"] = (_i64, [_i64, _i64, _i32])
+SIGNATURES["clane_csr_spmm_f32"] = (
+    C.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _p])
+SIGNATURES["clane_csr_row_sums_f32"] = (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p])
 
 
 def probe_padded_classes(C_: int) -> int:
@@ -572,6 +578,23 @@ class KernelBackend(abc.ABC):
     def project_affine(self, Z, d: int, rows, mu, W, Y):
         """Y[i, :m] = W (Z[rows[i], :d] - mu), W [m, d]; Y in Z's dtype, rounded once."""
         raise NotImplementedError(f"{type(self).__name__} has no project_affine")
+
+    # sparse content (sparse.py, ContentPCA.fit_sparse): optional in the same way.  S is a sparse.SparseRows on the device
+    # (validated CSR, its long rows listed in segments of csr_spmm_segment() non-zeros); everything dense is float32.
+    def csr_spmm_segment(self) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no csr_spmm_segment")
+
+    def csr_spmm_ws_len(self, n_rows: int, nnz: int, l: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no csr_spmm_ws_len")
+
+    def csr_spmm(self, S, B, l: int, out, a=None, s=None, ws=None):
+        """out[r, :l] = sum_e val[e] B[col[e], :l] - a[r] s[:l] over the non-zeros of row r (a None: ones; s None: no
+        epilogue); l a multiple of 4 up to 512; columns past l of B and out are neither read nor written."""
+        raise NotImplementedError(f"{type(self).__name__} has no csr_spmm")
+
+    def csr_row_sums(self, S, sums, ws=None):
+        """sums[r] (float64) = the sum of the values of row r, in a fixed order."""
+        raise NotImplementedError(f"{type(self).__name__} has no csr_row_sums")
 
     # owned class rows (csrc/spmm_update.h, spmm_owned_kernel): optional in the same way -- a backend without them keeps
     # every class row on spmm_update_class, and SweepEngine asks `has_spmm_owned` before it plans for them
@@ -1221,6 +1244,62 @@ class HipKernels(KernelBackend):
         self._invoke(self._fn("clane_project_affine", Z.dtype), "clane_project_affine",
                      zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n,
                      None if mu is None else _vec(mu, acc, "mu"), _vec(W, acc, "W"), m, yp, ldy, self._stream(Z))
+
+    # -- sparse content ---------------------------------------------------------------------
+    def csr_spmm_segment(self) -> int:
+        return int(self.lib.clane_csr_spmm_segment())
+
+    def csr_spmm_ws_len(self, n_rows: int, nnz: int, l: int) -> int:
+        return int(self.lib.clane_csr_spmm_ws_len(n_rows, nnz, l))
+
+    @staticmethod
+    def _csr_items(S, what: str):
+        long_rows, seg_ptr, item_long = S.segments()
+        if long_rows.dtype != torch.int32 or seg_ptr.dtype != torch.int64 or item_long.dtype != torch.int32 \
+                or seg_ptr.numel() != long_rows.numel() + 1:
+            raise ValueError(f"{what}: the segment list must be (int32 long_rows, int64 seg_ptr, int32 item_long)")
+        return long_rows, seg_ptr, item_long
+
+    def csr_spmm(self, S, B, l: int, out, a=None, s=None, ws=None):
+        bp, ldb = _mat(B, "B")
+        op, ldo = _mat(out, "out")
+        n, D = S.shape
+        f32 = torch.float32
+        if B.dtype != f32 or out.dtype != f32 or B.shape[0] < D or B.shape[1] < l or out.shape[0] < n or out.shape[1] < l:
+            raise ValueError(f"csr_spmm: B must be float32 with at least {D} rows and out with at least {n} rows of "
+                             f"{l} columns")
+        if l < 4 or l % 4 or l > CSR_MAX_L:
+            raise ValueError(f"csr_spmm: l must be a multiple of 4 in [4, {CSR_MAX_L}], got {l}")
+        if (a is not None and a.numel() != n) or (s is not None and s.numel() < l):
+            raise ValueError(f"csr_spmm: a needs {n} entries and s {l}")
+        long_rows, seg_ptr, item_long = self._csr_items(S, "csr_spmm")
+        n_items = item_long.numel()
+        if n_items and ws is None:
+            ws = torch.empty(n_items * l, dtype=f32, device=out.device)
+        if n_items and ws.numel() < n_items * l:
+            raise ValueError(f"csr_spmm: ws needs {n_items * l} elements")
+        self._invoke(self.lib.clane_csr_spmm_f32, "clane_csr_spmm",
+                     _vec(S.rowptr, torch.int64, "rowptr"), _vec(S.col, torch.int32, "col"), _vec(S.val, f32, "val"),
+                     n, S.nnz, bp, D, ldb, l, None if a is None else _vec(a, f32, "a"),
+                     None if s is None else _vec(s, f32, "s"), _ptr(long_rows), _ptr(seg_ptr), _ptr(item_long),
+                     long_rows.numel(), n_items, None if not n_items else _vec(ws, f32, "ws"),
+                     0 if not n_items else ws.numel(), op, ldo, self._stream(out))
+
+    def csr_row_sums(self, S, sums, ws=None):
+        n = S.shape[0]
+        if sums.numel() != n:
+            raise ValueError(f"csr_row_sums: sums needs {n} doubles")
+        long_rows, seg_ptr, item_long = self._csr_items(S, "csr_row_sums")
+        n_items = item_long.numel()
+        if n_items and ws is None:
+            ws = torch.empty(n_items, dtype=torch.float64, device=sums.device)
+        if n_items and ws.numel() < n_items:
+            raise ValueError(f"csr_row_sums: ws needs {n_items} doubles")
+        self._invoke(self.lib.clane_csr_row_sums_f32, "clane_csr_row_sums",
+                     _vec(S.rowptr, torch.int64, "rowptr"), _vec(S.val, torch.float32, "val"), n, S.nnz,
+                     _ptr(long_rows), _ptr(seg_ptr), _ptr(item_long), long_rows.numel(), n_items,
+                     None if not n_items else _vec(ws, torch.float64, "ws"), 0 if not n_items else ws.numel(),
+                     _vec(sums, torch.float64, "sums"), self._stream(sums))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

@@ -21,6 +21,7 @@
 #include "link_rank.h"
 #include "pair_train.h"
 #include "projection.h"
+#include "sparse_rows.h"
 #include "spmm_update.h"
 
 namespace {
@@ -1085,6 +1086,79 @@ int project_affine(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const
     return check_launch("project_affine");
 }
 
+// ---- sparse rows (sparse_rows.h) ----------------------------------------------------------------------------------------
+inline int64_t csr_max_items(int64_t nnz) { return nnz > kCsrSegment ? 2 * (nnz / kCsrSegment) : 0; }
+
+inline int csr_check_items(const char *what, int64_t n_rows, int64_t nnz, const void *long_rows, const void *seg_ptr,
+                           const void *item_long, int64_t n_long, int64_t n_items) {
+    REQUIRE(n_long >= 0 && n_items >= n_long && n_long <= n_rows && n_items <= csr_max_items(nnz) &&
+                (n_long == 0 || n_items >= 2 * n_long),
+            "%s: %lld long rows in %lld segments cannot belong to %lld rows of %lld non-zeros", what, (long long)n_long,
+            (long long)n_items, (long long)n_rows, (long long)nnz);
+    REQUIRE(n_long == 0 || (long_rows && seg_ptr && item_long), "%s: null segment list", what);
+    return CLANE_OK;
+}
+
+int csr_spmm(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz, const float *B,
+             int64_t b_rows, int64_t ldb, int32_t l, const float *a, const float *s, const int32_t *long_rows,
+             const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, float *ws, int64_t ws_len,
+             float *out, int64_t ldo, void *stream) {
+    static_assert(kCsrSegment == CLANE_CSR_SEGMENT && kCsrMaxL == CLANE_CSR_MAX_L && kCsrSegment % kWave == 0,
+                  "header and kernel disagree");
+    REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX && nnz >= 0 && b_rows >= 0 && b_rows <= INT32_MAX && l >= 4 &&
+                l <= kCsrMaxL && l % 4 == 0 && ldb >= l && ldo >= l,
+            "csr_spmm: bad shape rows=%lld nnz=%lld b_rows=%lld l=%d ldb=%lld ldo=%lld", (long long)n_rows, (long long)nnz,
+            (long long)b_rows, l, (long long)ldb, (long long)ldo);
+    if (const int rc = csr_check_items("csr_spmm", n_rows, nnz, long_rows, seg_ptr, item_long, n_long, n_items)) return rc;
+    if (n_rows == 0) return CLANE_OK;
+    REQUIRE(rowptr && out && (nnz == 0 || (col && val && B)), "csr_spmm: null pointer");
+    REQUIRE(n_items == 0 || (ws && ws_len >= n_items * int64_t(l)), "csr_spmm: the workspace needs %lld elements",
+            (long long)(n_items * int64_t(l)));
+    REQUIRE(aligned16(B) && aligned16(out) && aligned16(ws) && aligned16(s) && ldb % 4 == 0 && ldo % 4 == 0,
+            "csr_spmm: B, out, ws and s must be 16-byte aligned, ldb and ldo multiples of 4");
+    const int rpb = rows_per_block(n_rows);
+    const int64_t item_blocks = ceil_div(n_items, int64_t(kWavesPerBlock));
+    const int64_t grid = item_blocks + ceil_div(n_rows, int64_t(rpb));
+    REQUIRE(grid <= INT32_MAX, "csr_spmm: %lld rows and %lld segments are too many for one launch", (long long)n_rows,
+            (long long)n_items);
+#define CLANE_CSR_LAUNCH(LPR, NP)                                                                                      \
+    csr_spmm_kernel<LPR, NP><<<unsigned(grid), kBlock, 0, (hipStream_t)stream>>>(                                      \
+        rowptr, col, val, n_rows, B, ldb, l, a, s, long_rows, seg_ptr, item_long, n_items, item_blocks, rpb, ws, out, ldo)
+    if (l <= 64) CLANE_CSR_LAUNCH(16, 1);
+    else if (l <= 128) CLANE_CSR_LAUNCH(32, 1);
+    else if (l <= 256) CLANE_CSR_LAUNCH(64, 1);
+    else CLANE_CSR_LAUNCH(64, 2);
+#undef CLANE_CSR_LAUNCH
+    if (n_long > 0)
+        csr_spmm_combine_kernel<<<unsigned(ceil_div(n_long, int64_t(kWavesPerBlock))), kBlock, 0, (hipStream_t)stream>>>(
+            long_rows, seg_ptr, n_long, l, a, s, ws, out, ldo);
+    return check_launch("csr_spmm");
+}
+
+int csr_row_sums(const int64_t *rowptr, const float *val, int64_t n_rows, int64_t nnz, const int32_t *long_rows,
+                 const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, double *ws,
+                 int64_t ws_len, double *sums, void *stream) {
+    REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX && nnz >= 0, "csr_row_sums: bad shape rows=%lld nnz=%lld",
+            (long long)n_rows, (long long)nnz);
+    if (const int rc = csr_check_items("csr_row_sums", n_rows, nnz, long_rows, seg_ptr, item_long, n_long, n_items))
+        return rc;
+    if (n_rows == 0) return CLANE_OK;
+    REQUIRE(rowptr && sums && (nnz == 0 || val), "csr_row_sums: null pointer");
+    REQUIRE(n_items == 0 || (ws && ws_len >= n_items), "csr_row_sums: the workspace needs %lld doubles",
+            (long long)n_items);
+    const int rpb = rows_per_block(n_rows);
+    const int64_t item_blocks = ceil_div(n_items, int64_t(kWavesPerBlock));
+    const int64_t grid = item_blocks + ceil_div(n_rows, int64_t(rpb));
+    REQUIRE(grid <= INT32_MAX, "csr_row_sums: %lld rows and %lld segments are too many for one launch", (long long)n_rows,
+            (long long)n_items);
+    csr_row_sums_kernel<<<unsigned(grid), kBlock, 0, (hipStream_t)stream>>>(rowptr, val, n_rows, long_rows, seg_ptr,
+                                                                            item_long, n_items, item_blocks, rpb, ws, sums);
+    if (n_long > 0)
+        csr_row_sums_combine_kernel<<<unsigned(ceil_div(n_long, int64_t(kBlock))), kBlock, 0, (hipStream_t)stream>>>(
+            long_rows, seg_ptr, n_long, ws, sums);
+    return check_launch("csr_row_sums");
+}
+
 
 }  // namespace
 
@@ -1550,6 +1624,25 @@ CLANE_PCA_WRAPPERS(bf16, uint16_t, bf16_t, float)
 int64_t clane_column_sums_ws_len(int64_t n, int32_t d) { return (pca_chunks(n) > 0 ? pca_chunks(n) : 1) * int64_t(d > 0 ? d : 0); }
 int64_t clane_gram_ws_len(int64_t n, int32_t d) {
     return (pca_chunks(n) > 0 ? pca_chunks(n) : 1) * int64_t(d > 0 ? d : 0) * int64_t(d > 0 ? d : 0);
+}
+
+int clane_csr_spmm_segment(void) { return kCsrSegment; }
+int64_t clane_csr_spmm_ws_len(int64_t n_rows, int64_t nnz, int32_t l) {
+    (void)n_rows;                                /* a row of more than a segment is cut into fewer than 2 len / segment */
+    const int64_t items = csr_max_items(nnz > 0 ? nnz : 0);
+    return (items > 0 ? items : 1) * int64_t(l > 0 ? l : 0);
+}
+int clane_csr_spmm_f32(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz,
+                       const float *B, int64_t b_rows, int64_t ldb, int32_t l, const float *a, const float *s,
+                       const int32_t *long_rows, const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long,
+                       int64_t n_items, float *ws, int64_t ws_len, float *out, int64_t ldo, void *stream) {
+    return csr_spmm(rowptr, col, val, n_rows, nnz, B, b_rows, ldb, l, a, s, long_rows, seg_ptr, item_long, n_long, n_items,
+                    ws, ws_len, out, ldo, stream);
+}
+int clane_csr_row_sums_f32(const int64_t *rowptr, const float *val, int64_t n_rows, int64_t nnz, const int32_t *long_rows,
+                           const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, double *ws,
+                           int64_t ws_len, double *sums, void *stream) {
+    return csr_row_sums(rowptr, val, n_rows, nnz, long_rows, seg_ptr, item_long, n_long, n_items, ws, ws_len, sums, stream);
 }
 
 }  // extern "C"

@@ -646,6 +646,39 @@ class Graph(torch.utils.data.Dataset):
         self.X, self.d, self.content_transform = Y.contiguous(), int(Y.shape[1]), pca
         return pca
 
+    def reduce_sparse_content(self, S, dim: int, center: bool = True, whiten: bool = False, oversample: int = 16,
+                              power_iterations: int = 4, seed: int = 0, transform=None):
+        """As ``reduce_content`` for content that is a ``sparse.SparseRows`` [len(self), D] (a bag of words as CSR): the
+        randomized fit ``ContentPCA.fit_sparse`` and one CSR product replace ``X`` (whatever it held: without a dense
+        content file it is the constructor's N(0, 1) placeholder) and ``d``; the matrix is never made dense.
+        ``transform``: apply this fitted / loaded ``ContentPCA`` instead of fitting.  Returns the ``ContentPCA``."""
+        from .reduce import ContentPCA
+        from .sparse import SparseRows
+        if self._engine is not None:
+            raise RuntimeError("reduce_sparse_content: this graph's engine exists already and its tables have the "
+                               "content's width; reduce the content before the first build_P / iterate / engine()")
+        if self._Z_host is not None:
+            raise RuntimeError("reduce_sparse_content: embeddings were set (set_Z / Vertex.z) at the content's width; "
+                               "reduce the content first")
+        if not isinstance(S, SparseRows):
+            raise ValueError(f"reduce_sparse_content: expected a SparseRows, got {type(S).__name__}")
+        if S.shape[0] != len(self):
+            raise ValueError(f"reduce_sparse_content: the content has {S.shape[0]} rows, the graph {len(self)} vertices")
+        if transform is not None:
+            pca = transform
+        else:
+            pca = ContentPCA(dim, center=center, whiten=whiten)
+            pca._check_fit_shape(*S.shape)                       # before the upload
+        from . import _hip
+        Sd = S if S.device.type == "cuda" else S.to(_hip.require_gpu(None))
+        if transform is None:
+            pca.fit_sparse(Sd, oversample=oversample, power_iterations=power_iterations, seed=seed)
+            pca.sparse_fit_ = {"nnz": S.nnz, "oversample": int(oversample), "power_iterations": int(power_iterations),
+                               "seed": int(seed)}
+        Y = pca.transform_sparse(Sd, dtype=self.X.dtype).to(self.X.device)
+        self.X, self.d, self.content_transform = Y.contiguous(), int(Y.shape[1]), pca
+        return pca
+
     def project(self, dim: int = 2, table: str = "Z", vertices=None, whiten: bool = False):
         """``(Y [len(vertices), dim] on the host in vertex order, the fitted ContentPCA)``: the principal components of
         the CURRENT embeddings (``table="X"``: of the content) of ``vertices`` (default: all) -- the picture of an

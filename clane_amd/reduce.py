@@ -8,10 +8,15 @@ float64 on the host.
 Every sum runs in a fixed order, and a matrix that is streamed in blocks gives the bits of one call: a fit is
 reproducible bit for bit, whatever ``block_rows``.
 
+Sparse content (a bag of words as CSR, sparse.SparseRows) never becomes dense: ``fit_sparse`` is the randomized range
+finder with power iterations (Halko, Martinsson, Tropp 2011), its products the CSR kernels of csrc/sparse_rows.h, the
+centring a rank-one epilogue of those products, the ``l x l`` eigen-problems and the final SVD float64 on the host.
+
 There is no CPU fallback: without the library or a GPU, ``fit`` and ``transform`` raise ``ClaneHipError``.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from pathlib import Path
 from typing import Optional
@@ -25,7 +30,11 @@ CHUNK_ROWS = 2048                   # kGradChunk: the rows of one partial sum
 BLOCK_BYTE_BUDGET = 1 << 30         # a block of X on the device plus the Gram's workspace for it
 MAX_CHUNKS = 65535                  # chunks of one launch
 
-SECTION_KEYS = ("dim", "center", "whiten", "load")
+SECTION_KEYS = ("dim", "center", "whiten", "load", "sparse", "oversample", "power_iterations", "seed")
+SPARSE_DEFAULTS = {"oversample": 16, "power_iterations": 4, "seed": 0}
+MAX_SKETCH = 512                    # CLANE_CSR_MAX_L: dim + oversample
+RANK_TOL = 1e-6                     # eigenvalues (squared singular values) below RANK_TOL * the largest are dropped: fp32
+                                    # sums of up to n terms leave noise of about that size in a Gram
 NPZ_KEYS = ("components", "mean", "explained_variance", "explained_variance_ratio", "total_variance", "n_samples",
             "dim", "center", "whiten")
 
@@ -87,7 +96,44 @@ def check_section(section, world_size: int = 1) -> dict:
         if not isinstance(val, bool):
             raise ValueError(f"content_reduction: {key} must be true or false, got {val!r}")
         out[key] = val
+    sparse = section.get("sparse")
+    if sparse is None:
+        extra = sorted(set(section) & set(SPARSE_DEFAULTS))
+        if extra:
+            raise ValueError(f"content_reduction: {extra} belong to `sparse` (the randomized fit of a CSR content file)")
+        return out
+    if not isinstance(sparse, str) or not sparse:
+        raise ValueError(f"content_reduction: sparse must be the path of a CSR .npz file, got {sparse!r}")
+    out["sparse"] = sparse
+    for key, default in SPARSE_DEFAULTS.items():
+        val = section.get(key, default)
+        if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+            raise ValueError(f"content_reduction: {key} must be a non-negative integer, got {val!r}")
+        out[key] = val
+    if dim is not None and dim + out["oversample"] > MAX_SKETCH:
+        raise ValueError(f"content_reduction: dim + oversample = {dim + out['oversample']} exceeds {MAX_SKETCH}")
     return out
+
+
+def resolve_sparse(section: dict, data_root: Path):
+    """The validated ``SparseRows`` of the section's ``sparse`` file (relative to ``data_root``); None without the key.
+    A data root that also holds ``C.npy`` or ``C.pt`` is ambiguous: an error."""
+    if section.get("sparse") is None:
+        return None
+    from .sparse import SparseRows
+    path = Path(section["sparse"])
+    if not path.is_absolute():
+        path = Path(data_root) / path
+    if not path.is_file():
+        raise ValueError(f"content_reduction: sparse: {str(path)!r} is missing")
+    dense = [name for name in ("C.npy", "C.pt") if (Path(data_root) / name).exists()]
+    if dense:
+        raise ValueError(f"content_reduction: sparse: {str(data_root)!r} also holds {dense}: which content is meant is "
+                         f"ambiguous")
+    try:
+        return SparseRows.load_npz(path)
+    except ValueError as e:
+        raise ValueError(f"content_reduction: sparse: {e}") from None
 
 
 def resolve_load(section: dict, data_root: Path) -> Optional[Path]:
@@ -130,6 +176,7 @@ class ContentPCA:
         self.fitted_from = None                      # "fit" or "load"
         self.components_ = self.mean_ = self.explained_variance_ = self.explained_variance_ratio_ = None
         self.total_variance_ = self.n_samples_ = None
+        self.sparse_fit_ = None                      # {"nnz", "oversample", "power_iterations", "seed"} of a sparse run
 
     # ---- checks: before any launch --------------------------------------------------------------------------------
     def _check_fit_shape(self, n: int, d: int):
@@ -234,6 +281,154 @@ class ContentPCA:
             vertices = torch.arange(engine.V)
         return table_and_rows(engine, vertices, table)
 
+    # ---- sparse content: the randomized fit ------------------------------------------------------------------------------
+    @staticmethod
+    def _on(dev):
+        return torch.cuda.device(dev) if torch.device(dev).type == "cuda" else contextlib.nullcontext()
+
+    def _orthonormalise(self, k, Y: torch.Tensor, rows: torch.Tensor, what: str) -> torch.Tensor:
+        """``Y W^T`` with ``W = Lambda^{-1/2} V^T`` from the float64 ``eigh`` of ``Y^T Y``: orthonormal columns where the
+        eigenvalue is above RANK_TOL of the largest, zero columns behind them."""
+        m, lp = int(Y.shape[0]), int(Y.shape[1])
+        step = default_block_rows(lp, Y.dtype)
+        G = torch.zeros(lp, lp, dtype=Y.dtype, device=Y.device)
+        ws = torch.empty(k.gram_ws_len(min(step, m), lp), dtype=Y.dtype, device=Y.device)
+        for i, a in enumerate(range(0, m, step)):
+            k.gram(Y, lp, rows[a:a + step], None, ws, G, accumulate=i > 0)
+        lam, vec = torch.linalg.eigh(G.cpu().double())
+        lam, vec = torch.flip(lam, [0]), torch.flip(vec, [1])
+        keep = lam > RANK_TOL * float(lam[0]) if float(lam[0]) > 0 else torch.zeros_like(lam, dtype=torch.bool)
+        r = int(keep.sum())
+        if r == 0:
+            raise ValueError(f"ContentPCA: the content has no variance left in {what} (numerical rank 0)")
+        W = torch.zeros(lp, lp, dtype=torch.float64)
+        W[:r] = (vec[:, :r] / lam[:r].sqrt()).T
+        Q = torch.empty_like(Y)
+        Wd = W.to(Y.dtype).to(Y.device)
+        for a in range(0, m, step):
+            k.project_affine(Y, lp, rows[a:a + step], None, Wd, Q[a:a + step])
+        return Q
+
+    def fit_sparse(self, S, oversample: int = 16, power_iterations: int = 4, seed: int = 0) -> "ContentPCA":
+        """Fit on a ``sparse.SparseRows`` [n, D] without densifying it: the randomized range finder with
+        ``power_iterations`` rounds on a sketch of ``l = min(dim + oversample, D, n)`` columns, Omega drawn N(0, 1) from
+        a CPU generator seeded with ``seed``.  The same seed gives the same bits."""
+        from .sparse import SparseRows
+        if not isinstance(S, SparseRows):
+            raise ValueError(f"ContentPCA.fit_sparse: expected a SparseRows, got {type(S).__name__}")
+        for name, v in (("oversample", oversample), ("power_iterations", power_iterations), ("seed", seed)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f"ContentPCA.fit_sparse: {name} must be a non-negative integer, got {v!r}")
+        n, D = S.shape
+        self._check_fit_shape(n, D)
+        if self.dim + int(oversample) > MAX_SKETCH:
+            raise ValueError(f"ContentPCA.fit_sparse: dim + oversample = {self.dim + int(oversample)} exceeds {MAX_SKETCH}")
+        dev = S.device if S.device.type == "cuda" else _hip.require_gpu(self.device)
+        k = _hip.kernels()
+        l = min(self.dim + int(oversample), D, n)
+        lp = -(-l // 4) * 4
+        f32, f64 = torch.float32, torch.float64
+        with self._on(dev):
+            S = S if S.device == dev else S.to(dev)
+            St = S.transposed()
+            rows_n = torch.arange(n, dtype=torch.int32, device=dev)
+            rows_D = torch.arange(D, dtype=torch.int32, device=dev)
+            if self.center:
+                sums = torch.empty(D, dtype=f64, device=dev)
+                k.csr_row_sums(St, sums)
+                mean = (sums.cpu() / n).to(f32)                      # rounded to float32: what the products subtract
+            else:
+                mean = torch.zeros(D, dtype=f32)
+            mu64 = mean.double()
+            mu = mean.to(dev) if self.center else None
+            total = (S.sum_squares() - n * float(mu64 @ mu64)) / (n - 1)
+            Omega = torch.zeros(D, lp, dtype=f32)
+            Omega[:, :l] = torch.randn(D, l, generator=torch.Generator().manual_seed(int(seed)), dtype=f32)
+
+            def times_S(Z_host_or_dev):                               # S Z - 1 (mu^T Z), Z [D, lp]
+                Zd = Z_host_or_dev.to(dev)
+                s = (mu64 @ Z_host_or_dev.cpu().double()).to(f32).to(dev) if self.center else None
+                Y = torch.empty(n, lp, dtype=f32, device=dev)
+                k.csr_spmm(S, Zd, lp, Y, a=None, s=s)
+                return Y
+
+            def times_St(Q):                                          # S^T Q - mu (1^T Q), Q [n, lp]
+                s = None
+                if self.center:
+                    cs = torch.empty(lp, dtype=f64, device=dev)
+                    cws = torch.empty(k.column_sums_ws_len(n, lp), dtype=f64, device=dev)
+                    k.column_sums(Q, lp, rows_n, cws, cs)
+                    s = cs.to(f32)
+                Z = torch.empty(D, lp, dtype=f32, device=dev)
+                k.csr_spmm(St, Q, lp, Z, a=mu, s=s)
+                return Z
+
+            Q = self._orthonormalise(k, self._orthonormalise(k, times_S(Omega), rows_n, "S Omega"), rows_n, "S Omega")
+            for _ in range(int(power_iterations)):
+                Z = times_St(Q)
+                Z = self._orthonormalise(k, self._orthonormalise(k, Z, rows_D, "S^T Q"), rows_D, "S^T Q")
+                Q = times_S(Z)
+                Q = self._orthonormalise(k, self._orthonormalise(k, Q, rows_n, "S Z"), rows_n, "S Z")
+            B = times_St(Q).cpu()
+        _, sig, Vt = np.linalg.svd(B.double().numpy().T, full_matrices=False)
+        lam = sig ** 2
+        rank = int((lam > RANK_TOL * lam[0]).sum()) if lam[0] > 0 else 0
+        if rank < self.dim:
+            raise ValueError(f"ContentPCA: dim = {self.dim} needs a positive variance in every kept component; component "
+                             f"{rank} of {self.dim} has none (numerical rank {rank} of D = {D})")
+        var = lam[:self.dim] / (n - 1)
+        self.components_, self.mean_ = fix_signs(Vt[:self.dim]), mu64.numpy().copy()
+        self.explained_variance_ = var.copy()
+        self.explained_variance_ratio_ = var / total if total > 0 else np.zeros_like(var)
+        self.total_variance_, self.n_samples_ = float(total), int(n)
+        self.fitted_from = "fit"
+        return self
+
+    def transform_sparse(self, S, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """``(S - 1 mean_^T) components_^T`` (whitened under ``whiten``) for a ``SparseRows``: one CSR product, summed in
+        float32 and rounded once to ``dtype``; on ``S``'s device."""
+        from .sparse import SparseRows
+        if not isinstance(S, SparseRows):
+            raise ValueError(f"ContentPCA.transform_sparse: expected a SparseRows, got {type(S).__name__}")
+        if self.components_ is None:
+            raise ValueError("ContentPCA: fit or load a transform first")
+        _hip.acc_dtype(dtype)
+        n, D = S.shape
+        if D != self.components_.shape[1]:
+            raise ValueError(f"ContentPCA.transform_sparse: the transform was fitted on {self.components_.shape[1]} "
+                             f"columns, S has {D}")
+        if self.dim > MAX_SKETCH:
+            raise ValueError(f"ContentPCA.transform_sparse: dim = {self.dim} exceeds {MAX_SKETCH}")
+        home = S.device
+        if n == 0:
+            return torch.empty(0, self.dim, dtype=dtype, device=home)
+        dev = home if home.type == "cuda" else _hip.require_gpu(self.device)
+        W = torch.from_numpy(np.ascontiguousarray(self.components_, dtype=np.float64))
+        if self.whiten:
+            var = torch.from_numpy(np.ascontiguousarray(self.explained_variance_, dtype=np.float64))
+            if bool((var <= 0).any()):
+                raise ValueError("ContentPCA: whiten needs a positive variance in every kept component")
+            W = W / var.sqrt()[:, None]
+        mp = -(-self.dim // 4) * 4
+        Wt = torch.zeros(D, mp, dtype=torch.float32)
+        Wt[:, :self.dim] = W.T.to(torch.float32)
+        s = None
+        if self.center:
+            s = torch.zeros(mp, dtype=torch.float32)
+            s[:self.dim] = (Wt[:, :self.dim].double().T @ torch.from_numpy(self.mean_)).to(torch.float32)
+        k = _hip.kernels()
+        with self._on(dev):
+            Sd = S if home == dev else S.to(dev)
+            out = torch.empty(n, mp, dtype=torch.float32, device=dev)
+            k.csr_spmm(Sd, Wt.to(dev), mp, out, a=None, s=None if s is None else s.to(dev))
+            Y = out[:, :self.dim].to(dtype).contiguous()
+        return Y if home == dev else Y.to(home)
+
+    def fit_transform_sparse(self, S, oversample: int = 16, power_iterations: int = 4, seed: int = 0,
+                             dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        return self.fit_sparse(S, oversample=oversample, power_iterations=power_iterations,
+                               seed=seed).transform_sparse(S, dtype=dtype)
+
     # ---- transform ------------------------------------------------------------------------------------------------
     def _weights(self, dtype, dev):
         if self.components_ is None:
@@ -326,6 +521,9 @@ class ContentPCA:
     def report(self, in_width: int) -> dict:
         """What the CLI writes as ``content_reduction.json``."""
         ratios = [float(r) for r in self.explained_variance_ratio_]
-        return {"input_width": int(in_width), "output_width": self.dim, "n": int(self.n_samples_),
-                "explained_variance_ratio": ratios, "explained_variance_ratio_sum": float(sum(ratios)),
-                "center": self.center, "whiten": self.whiten, "source": self.fitted_from}
+        out = {"input_width": int(in_width), "output_width": self.dim, "n": int(self.n_samples_),
+               "explained_variance_ratio": ratios, "explained_variance_ratio_sum": float(sum(ratios)),
+               "center": self.center, "whiten": self.whiten, "source": self.fitted_from}
+        if self.sparse_fit_ is not None:                     # set by Graph.reduce_sparse_content
+            out.update(method="randomized", **self.sparse_fit_)
+        return out

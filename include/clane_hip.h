@@ -67,7 +67,10 @@ extern "C" {
                              *    clane_gram_ws_len (content reduction: the device passes of a PCA on rows of a table --
                              *    deterministic column sums, the centred Gram on the matrix cores, an affine projection)
                              *    + clane_spmm_update_owned_f32 (class rows summed in LDS by row-owning workgroups: no slab,
-                             *    no combine pass; embedder.py:90-92) */
+                             *    no combine pass; embedder.py:90-92)
+                             *    + clane_csr_spmm_f32, clane_csr_row_sums_f32, clane_csr_spmm_segment, clane_csr_spmm_ws_len
+                             *    (sparse content: CSR rows times a dense matrix with a rank-one epilogue and the rows'
+                             *    value sums -- the products of a randomized PCA on a bag of words) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -799,6 +802,39 @@ int clane_project_affine_f64(const double *Z, int64_t table_rows, int32_t d, int
 int clane_project_affine_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,
                               int64_t n, const float *mu, const float *W, int32_t m, uint16_t *Y, int64_t ldy,
                               void *stream);
+
+/* ---- sparse rows (csrc/sparse_rows.h) -----------------------------------------------------------------------------------
+ * A CSR matrix of n_rows rows and nnz non-zeros: rowptr int64 [n_rows + 1] (rowptr[0] may be any offset into col / val: a
+ * slice of another matrix's rowptr describes a sub-matrix), col int32 (rows of B, in [0, b_rows): NOT checked here, the
+ * caller validates), val fp32.  n_rows and b_rows are below 2^31.
+ *
+ * csr_spmm: out[r, 0:l) = sum_e val[e] B[col[e], 0:l) - a[r] s[0:l), e in [rowptr[r], rowptr[r + 1]).  a NULL: a[r] = 1;
+ *   s NULL: no epilogue.  B [b_rows, ldb >= l], out [n_rows, ldo >= l]; columns past l are never read or written.  l is a
+ *   multiple of 4 in [4, CLANE_CSR_MAX_L]; B, out, s and ws 16-byte aligned, ldb and ldo multiples of 4.
+ * A row of more than CLANE_CSR_SEGMENT (= clane_csr_spmm_segment()) non-zeros is cut into segments of that length (the
+ *   last one shorter), listed by the caller: long_rows int32 [n_long] the long rows ascending, seg_ptr int64 [n_long + 1]
+ *   the prefix sums of their segment counts ceil(len / segment), item_long int32 [n_items] the index into long_rows of
+ *   every segment (n_items = seg_ptr[n_long]).  Segments write partial sums to ws (n_items * l floats, at most
+ *   clane_csr_spmm_ws_len(n_rows, nnz, l)); a second kernel adds them in segment order and applies the epilogue.
+ * Order of every element's sum: inside a segment (a short row is one) the wave's EPW sub-waves (EPW = 4 for l <= 64, 2
+ *   for l <= 128, else 1) each add the non-zeros k = sub, sub + EPW, .. of the segment in ascending k by one fmaf onto +0;
+ *   the sub-wave sums are folded (s0 + s2) + (s1 + s3) resp. s0 + s1; segments are added in order onto the first one;
+ *   the epilogue is one fmaf(-a[r], s[c], sum).  The bits of a row depend on the row and on l alone: not on the grid,
+ *   not on the other rows of the call.
+ * csr_row_sums: sums[r] (double) = the sum of the row's values: lane t of 64 adds a segment's values t, t + 64, .. in
+ *   order, the lanes are folded by the xor butterfly (32, 16, .., 1), segments are added in order.  ws: n_items doubles.
+ * No allocation, no synchronisation, no atomics on memory; two calls give the same bits. */
+#define CLANE_CSR_SEGMENT 2048
+#define CLANE_CSR_MAX_L 512
+int clane_csr_spmm_segment(void);
+int64_t clane_csr_spmm_ws_len(int64_t n_rows, int64_t nnz, int32_t l);
+int clane_csr_spmm_f32(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz,
+                       const float *B, int64_t b_rows, int64_t ldb, int32_t l, const float *a, const float *s,
+                       const int32_t *long_rows, const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long,
+                       int64_t n_items, float *ws, int64_t ws_len, float *out, int64_t ldo, void *stream);
+int clane_csr_row_sums_f32(const int64_t *rowptr, const float *val, int64_t n_rows, int64_t nnz, const int32_t *long_rows,
+                           const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, double *ws,
+                           int64_t ws_len, double *sums, void *stream);
 
 #ifdef __cplusplus
 }
