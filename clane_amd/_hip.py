@@ -25,6 +25,7 @@ ABI_VERSION = 5
 SCORE_REFERENCE, SCORE_PER_EDGE, SCORE_RAW_DOT = 0, 1, 2
 SPMM_SINKS_UNTOUCHED = 1
 SPMM_TABLE_BEYOND_CACHE = 2
+OWNED_EPILOGUE_AHEAD = 1 << 16      # CLANE_OWNED_EPILOGUE_AHEAD
 SCORE_FUSE_SOFTMAX = 1
 SCORE_MODES = {"reference": SCORE_REFERENCE, "per_edge": SCORE_PER_EDGE, "raw_dot": SCORE_RAW_DOT}
 
@@ -71,6 +72,14 @@ for _s in ("f32", "f64", "bf16"):
     SIGNATURES[f"clane_l1_distance_{_s}"] = (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p])
 SIGNATURES["clane_spmm_update_owned_f32"] = (
     C.c_int, [_p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _p, _p])
+# every column tile of a K3 pass in one launch (csrc/spmm_update.h, the *_tiles_kernel forms)
+SIGNATURES["clane_spmm_update_tiles_f32"] = (
+    C.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _i64, _i32, _p, _i64, _p])
+SIGNATURES["clane_spmm_update_class_tiles_f32"] = (
+    C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32,
+              _i32, _p, _p, _i64, _p])
+SIGNATURES["clane_spmm_update_owned_tiles_f32"] = (
+    C.c_int, [_p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _i32, _p, _i64, _p])
 for _s in ("f32", "f64"):
     SIGNATURES[f"clane_degree_weighted_sums_{_s}"] = (C.c_int, [_p, _p, _p, _i64, _p, _p, _p])
     SIGNATURES[f"clane_edge_score_finalize_{_s}"] = (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p])
@@ -607,10 +616,39 @@ class KernelBackend(abc.ABC):
         raise NotImplementedError(f"{type(self).__name__} has no make_owned_plan")
 
     def spmm_update_owned(self, colidx, P, plan, block_threads: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
-                          partials, beyond_cache: bool = False, loads: int = 0):
+                          partials, beyond_cache: bool = False, loads: int = 0, ahead: bool = False):
         """The class rows of `plan` summed in LDS by row-owning workgroups, then the usual epilogue; writes
-        partials[row_part[j]] for every row of the plan."""
+        partials[row_part[j]] for every row of the plan.  `ahead`: the epilogue requests the next rows' x / z_old before
+        it finishes the current ones (no result depends on it; a backend may ignore it)."""
         raise NotImplementedError(f"{type(self).__name__} has no spmm_update_owned")
+
+    # every column tile of a pass in one launch (csrc/spmm_update.h, the *_tiles_kernel forms): optional in the same way --
+    # a backend without them keeps one launch per tile, and SweepEngine asks `has_spmm_tiles` before it plans for them.
+    # Each takes the WHOLE tables (d columns) and `tile_cols`; tile t's partials start at partials[t * partials_stride].
+    def has_spmm_tiles(self, dtype, d: int, tile_cols: int) -> bool:
+        """Whether the spmm_update*_tiles calls take tables of `dtype`, `d` columns wide, in tiles of `tile_cols`."""
+        return False
+
+    owned_epilogue_ahead = False        # whether spmm_update_owned* take `ahead`: only then is it ever passed
+
+    def spmm_update_tiles(self, rowptr, colidx, P, nrows: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
+                          tile_cols: int, long_threshold: int, partials, partials_stride: int,
+                          sinks_untouched: bool = False, beyond_cache: bool = False):
+        """spmm_update for every column tile, one launch."""
+        raise NotImplementedError(f"{type(self).__name__} has no spmm_update_tiles")
+
+    def spmm_update_class_tiles(self, colidx, P, item_e0, item_len, item_slot, items_per_block: int, class_rows, slot_ptr,
+                                n_slots: int, row0: int, Z_old, X, gamma: float, Z_new, d: int, tile_cols: int, slab,
+                                partials, partials_stride: int, beyond_cache: bool = False):
+        """spmm_update_class for every column tile: one chunk launch and one combine launch; `slab` holds
+        tiles * spmm_class_slab_len(n_slots, tile_cols) elements."""
+        raise NotImplementedError(f"{type(self).__name__} has no spmm_update_class_tiles")
+
+    def spmm_update_owned_tiles(self, colidx, P, plan, block_threads: int, row0: int, Z_old, X, gamma: float, Z_new,
+                                d: int, tile_cols: int, partials, partials_stride: int, beyond_cache: bool = False,
+                                loads: int = 0, ahead: bool = False):
+        """spmm_update_owned for every column tile, the tile loop inside the persistent workgroups."""
+        raise NotImplementedError(f"{type(self).__name__} has no spmm_update_owned_tiles")
 
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
@@ -628,6 +666,8 @@ class KernelBackend(abc.ABC):
 
 class HipKernels(KernelBackend):
     """Tensor-level view of the C ABI.  One instance per process is enough (stateless)."""
+
+    owned_epilogue_ahead = True         # spmm_update_owned* take `ahead` (CLANE_OWNED_EPILOGUE_AHEAD)
 
     def __init__(self, lib: Optional[C.CDLL] = None):
         self.lib = lib if lib is not None else load_library()
@@ -862,9 +902,10 @@ class HipKernels(KernelBackend):
         return OwnedPlan(plan, chunk, device)
 
     def spmm_update_owned(self, colidx, P, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X, gamma: float,
-                          Z_new, d: int, partials, beyond_cache: bool = False, loads: int = 0):
+                          Z_new, d: int, partials, beyond_cache: bool = False, loads: int = 0, ahead: bool = False):
         """Class rows summed in LDS by row-owning workgroups (no slab, no combine); writes partials[row_part[j]].
-        `loads`: CLANE_OWNED_LOADS, row loads in flight per wave (0 = the chunk kernel's choice)."""
+        `loads`: CLANE_OWNED_LOADS, row loads in flight per wave (0 = the chunk kernel's choice); `ahead`:
+        CLANE_OWNED_EPILOGUE_AHEAD."""
         zo, ldz = _mat(Z_old, "Z_old")
         xp, ldx = _mat(X, "X")
         zn, ldo = _mat(Z_new, "Z_new")
@@ -879,8 +920,86 @@ class HipKernels(KernelBackend):
         self._invoke(self.lib.clane_spmm_update_owned_f32, "clane_spmm_update_owned",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
                      int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
-                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8),
+                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8)
+                     | (OWNED_EPILOGUE_AHEAD if ahead else 0),
                      _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+
+    # -- every column tile of a pass in one launch ----------------------------------------------------------
+    def has_spmm_tiles(self, dtype, d: int, tile_cols: int) -> bool:
+        """fp32, tiles of whole 16-byte packs, and a last tile with the lane layout of a full one (the fused launch runs
+        one kernel instance for all tiles)."""
+        if dtype != torch.float32 or not 0 < tile_cols <= d or tile_cols % 4:
+            return False
+        lanes = lambda w: next(n for n in (8, 16, 32, 64) if -(-w // 4) <= n or n == 64)       # noqa: E731
+        return lanes(d - (-(-d // tile_cols) - 1) * tile_cols) == lanes(tile_cols)
+
+    def _tile_args(self, name, Z_old, X, Z_new, d, tile_cols, partials, partials_stride, per_tile):
+        """The three whole tables of a fused call and its partials, checked: (zo, ldz, xp, ldx, zn, ldo)."""
+        zo, ldz = _mat(Z_old, "Z_old")
+        xp, ldx = _mat(X, "X")
+        zn, ldo = _mat(Z_new, "Z_new")
+        if not (Z_old.dtype == X.dtype == Z_new.dtype == torch.float32):
+            raise TypeError(f"{name}: float32 tables only")
+        if not self.has_spmm_tiles(torch.float32, d, tile_cols) or min(Z_old.shape[1], X.shape[1], Z_new.shape[1]) < d:
+            raise ValueError(f"{name}: no fused launch for d={d} in tiles of {tile_cols} columns")
+        tiles = -(-d // tile_cols)
+        if (tiles > 1 and partials_stride < per_tile) or partials.numel() < (tiles - 1) * partials_stride + per_tile:
+            raise ValueError(f"{name}: the tiles' partials overlap or end outside `partials`")
+        return zo, ldz, xp, ldx, zn, ldo
+
+    def spmm_update_tiles(self, rowptr, colidx, P, nrows: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
+                          tile_cols: int, long_threshold: int, partials, partials_stride: int,
+                          sinks_untouched: bool = False, beyond_cache: bool = False):
+        """The row pass of every column tile in one launch: a tile-major grid of tiles x workgroups."""
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_tiles", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, self.spmm_partials_len(nrows, 0))
+        self._invoke(self.lib.clane_spmm_update_tiles_f32, "clane_spmm_update_tiles",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"),
+                     nrows, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols, long_threshold,
+                     (SPMM_SINKS_UNTOUCHED if sinks_untouched else 0) | (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
+
+    def spmm_update_class_tiles(self, colidx, P, item_e0, item_len, item_slot, items_per_block: int, class_rows, slot_ptr,
+                                n_slots: int, row0: int, Z_old, X, gamma: float, Z_new, d: int, tile_cols: int, slab,
+                                partials, partials_stride: int, beyond_cache: bool = False):
+        """Chunk + combine of every column tile, one launch each; tile t's chunk sums at
+        slab[t * spmm_class_slab_len(n_slots, tile_cols):]."""
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_class_tiles", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, class_rows.numel())
+        n_items = item_e0.numel()
+        if n_items % items_per_block or item_len.numel() != n_items or item_slot.numel() != n_items:
+            raise ValueError("spmm_update_class_tiles: the item arrays must hold whole blocks of items_per_block items")
+        if slab.numel() < -(-d // tile_cols) * self.spmm_class_slab_len(n_slots, tile_cols):
+            raise ValueError("spmm_update_class_tiles: the slab does not hold every tile's chunk sums")
+        self._invoke(self.lib.clane_spmm_update_class_tiles_f32, "clane_spmm_update_class_tiles",
+                     _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"),
+                     _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
+                     _vec(item_slot, torch.int32, "item_slot"), n_items // items_per_block, items_per_block,
+                     _vec(class_rows, torch.int32, "class_rows"), _vec(slot_ptr, torch.int64, "slot_ptr"),
+                     class_rows.numel(), n_slots, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
+                     SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0, _vec(slab, torch.float32, "slab"),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
+
+    def spmm_update_owned_tiles(self, colidx, P, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X, gamma: float,
+                                Z_new, d: int, tile_cols: int, partials, partials_stride: int, beyond_cache: bool = False,
+                                loads: int = 0, ahead: bool = False):
+        """The owned pass of every column tile in one launch: the tile loop runs inside the persistent workgroups."""
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_owned_tiles", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, plan.max_part + 1)
+        if not self.has_spmm_owned(torch.float32, tile_cols):
+            raise ValueError(f"spmm_update_owned_tiles: no owned instance for tiles of {tile_cols} columns")
+        lanes = 32 if tile_cols <= 128 else 64
+        if plan.max_batch_vrows * lanes * 16 > OWNED_LDS_LIMIT:
+            raise ValueError(f"spmm_update_owned_tiles: {plan.max_batch_vrows} virtual rows per batch do not fit the LDS")
+        if (plan.max_edge > min(colidx.numel(), P.numel()) or plan.max_row >= min(X.shape[0], Z_new.shape[0])
+                or row0 + plan.max_row >= Z_old.shape[0]):
+            raise ValueError("spmm_update_owned_tiles: the plan reaches outside colidx / P or the tables")
+        self._invoke(self.lib.clane_spmm_update_owned_tiles_f32, "clane_spmm_update_owned_tiles",
+                     _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
+                     int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
+                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8)
+                     | (OWNED_EPILOGUE_AHEAD if ahead else 0),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
 
     def reduce_partials(self, partials, n: int, ws, out):
         self._invoke(self.lib.clane_reduce_partials, "clane_reduce_partials",

@@ -526,12 +526,54 @@ constexpr int64_t kOwnedLdsReserve = 1024;
 constexpr int64_t kLdsPerCU = 160 * 1024;
 constexpr int64_t kLdsDefaultLimit = 64 * 1024;
 
+// Column tiles of one launch: tile t covers columns [t * tile_cols, min(d, (t + 1) * tile_cols)).  The fused calls pick
+// ONE kernel instance for all tiles, by the width of a full tile, so the last (narrower) tile must be one the per-tile
+// call would give the same lane layout: the callers REQUIRE tiles_share_layout.
+inline int tile_count(int d, int tile_cols) { return int(ceil_div(d, tile_cols)); }
+template <typename T>
+bool tiles_share_layout(int d, int tile_cols) {
+    constexpr int KV = Elem<T>::kVec;
+    auto lanes = [](int w) { const int p = int(ceil_div(w, KV)); return p <= 8 ? 8 : p <= 16 ? 16 : p <= 32 ? 32 : 64; };
+    return tile_cols % KV == 0 && lanes(d - (tile_count(d, tile_cols) - 1) * tile_cols) == lanes(tile_cols);
+}
+
+// spmm_update_owned over `n_tiles` column tiles of a table d_all wide (the per-tile call: one tile of d_all columns)
+template <typename T, typename PT>
+int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan,
+                           int32_t block_threads, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
+                           typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d_all, int32_t tile_cols,
+                           int64_t part_stride, int32_t flags, double *delta_partials, void *stream);
+
 template <typename T, typename PT>
 int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan, int32_t block_threads,
                       int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
                       typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t flags,
                       double *delta_partials, void *stream) {
+    return spmm_update_owned_impl<T, PT>("spmm_update_owned", colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx,
+                                         gamma, Z_new, ldo, d, d, 0, flags, delta_partials, stream);
+}
+
+template <typename T, typename PT>
+int spmm_update_owned_tiles(const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan, int32_t block_threads,
+                            int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
+                            typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t tile_cols,
+                            int32_t flags, double *delta_partials, int64_t partials_tile_stride, void *stream) {
+    REQUIRE(d > 0 && tile_cols > 0 && tile_cols <= d && partials_tile_stride >= 0 && tiles_share_layout<T>(d, tile_cols),
+            "spmm_update_owned_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the "
+            "lane layout, the partials' stride >= 0 (d=%d tile_cols=%d)", d, tile_cols);
+    return spmm_update_owned_impl<T, PT>("spmm_update_owned_tiles", colidx, P, plan, block_threads, row0, Z_old, ldz, X,
+                                         ldx, gamma, Z_new, ldo, d, tile_cols, partials_tile_stride, flags, delta_partials,
+                                         stream);
+}
+
+template <typename T, typename PT>
+int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan,
+                           int32_t block_threads, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
+                           typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d_all, int32_t tile_cols,
+                           int64_t part_stride, int32_t flags, double *delta_partials, void *stream) {
     using A = typename Elem<T>::acc_t;
+    const int32_t d = tile_cols;           // what the instance and the LDS sums are sized by: one full tile
+    REQUIRE(d_all >= d, "%s: bad shape", what);
     REQUIRE(plan, "spmm_update_owned: null plan");
     REQUIRE(plan->n_groups >= 0 && row0 >= 0 && d > 0, "spmm_update_owned: bad shape");
     REQUIRE(plan->n_steps >= 1 && plan->n_steps <= kOwnedMaxSteps, "spmm_update_owned: n_steps must be in [1, %d]",
@@ -539,7 +581,7 @@ int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan
     REQUIRE(plan->chunk >= kWave && plan->chunk % kWave == 0, "spmm_update_owned: chunk must be a positive multiple of 64");
     REQUIRE(block_threads >= kWave && block_threads <= kOwnedMaxBlock && block_threads % kWave == 0,
             "spmm_update_owned: block_threads must be a multiple of 64 in [64, %d]", kOwnedMaxBlock);
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_owned: leading dimension < d");
+    REQUIRE(ldz >= d_all && ldx >= d_all && ldo >= d_all, "spmm_update_owned: leading dimension < d");
     REQUIRE(plan->max_batch_vrows >= 0, "spmm_update_owned: negative max_batch_vrows");
     if (plan->n_groups == 0) return CLANE_OK;
     REQUIRE(colidx && P && plan->grp_bat_ptr && plan->bat_vrow_ptr && plan->bat_row_ptr && plan->bat_seg_ptr &&
@@ -574,7 +616,7 @@ int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan
             }
         }
         kernel<<<unsigned(plan->n_groups), unsigned(block_threads), size_t(lds), (hipStream_t)stream>>>(
-            colidx, P, op, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, beyond, delta_partials);
+            colidx, P, op, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d_all, tile_cols, part_stride, (flags & CLANE_OWNED_EPILOGUE_AHEAD) != 0, beyond, delta_partials);
     };
     constexpr int KV = Elem<T>::kVec;
     // Row loads in flight per wave.  Asked for through CLANE_OWNED_LOADS(n) (the instances: 6, 8, 12 at two rows per
@@ -592,7 +634,112 @@ int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan
         else launch.template operator()<KV, 64, 8>();
     }
     if (rc != CLANE_OK) return rc;
-    return check_launch("spmm_update_owned");
+    return check_launch(what);
+}
+
+// ---- every column tile of a pass in one launch (csrc/spmm_update.h, spmm_update_tiles_kernel) -----------------------
+template <typename T, typename PT>
+int spmm_update_tiles(const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows, int64_t row0,
+                      const T *Z_old, int64_t ldz, const T *X, int64_t ldx, typename Elem<T>::acc_t gamma, T *Z_new,
+                      int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold, int32_t flags,
+                      double *delta_partials, int64_t partials_tile_stride, void *stream) {
+    REQUIRE(nrows >= 0 && row0 >= 0 && d > 0, "spmm_update_tiles: bad shape nrows=%lld row0=%lld d=%d", (long long)nrows,
+            (long long)row0, d);
+    REQUIRE(tile_cols > 0 && tile_cols <= d && tiles_share_layout<T>(d, tile_cols),
+            "spmm_update_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the lane "
+            "layout (d=%d tile_cols=%d)", d, tile_cols);
+    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_tiles: leading dimension < d");
+    REQUIRE(long_threshold >= 0, "spmm_update_tiles: negative long_threshold");
+    REQUIRE(delta_partials, "spmm_update_tiles: null delta_partials");
+    const int n_tiles = tile_count(d, tile_cols);
+    const int per_tile = int(spmm_main_grid(nrows));
+    REQUIRE(partials_tile_stride >= (n_tiles > 1 ? per_tile : 0), "spmm_update_tiles: the tiles' partials overlap");
+    REQUIRE(int64_t(n_tiles) * per_tile <= INT32_MAX, "spmm_update_tiles: grid too large");
+    if (nrows == 0) return CLANE_OK;
+    REQUIRE(rowptr && colidx && P && Z_old && X && Z_new, "spmm_update_tiles: null pointer");
+    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_tiles: Z_new must not alias Z_old (Jacobi sweep)");
+    const Layout L = pick_layout<T>(tile_cols, {Z_old, X, Z_new}, {ldz, ldx, ldo});
+    REQUIRE(L.vec, "spmm_update_tiles: the tables must allow 16-byte packs");
+    const TileGrid tg{per_tile, tile_cols, partials_tile_stride};
+    const unsigned grid = unsigned(n_tiles) * unsigned(per_tile);
+    const bool sinks = (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {      // the instance spmm_update picks for a tile of tile_cols columns
+        if constexpr (VEC > 1) {
+            constexpr int U = CLANE_SPMM_U;
+            if constexpr (LPR == 32 && VEC == 4 && sizeof(T) == 4) {
+                if (beyond) {
+                    spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, CLANE_SUBROW_U32><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                        rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
+                        rows_per_block(nrows), beyond, tg, delta_partials);
+                    return;
+                }
+            }
+            if constexpr (LPR < kWave)
+                spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
+                    rows_per_block(nrows), beyond, tg, delta_partials);
+            else
+                spmm_update_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
+                    rows_per_block(nrows), beyond, tg, delta_partials);
+        }
+    });
+    return check_launch("spmm_update_tiles");
+}
+
+template <typename T, typename PT>
+int spmm_update_class_tiles(const int32_t *colidx, const PT *P, const int64_t *item_e0, const int32_t *item_len,
+                            const int32_t *item_slot, int64_t n_blocks, int32_t items_per_block,
+                            const int32_t *class_rows, const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots,
+                            int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
+                            typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t tile_cols,
+                            int32_t flags, typename Elem<T>::acc_t *slab, double *delta_partials,
+                            int64_t partials_tile_stride, void *stream) {
+    REQUIRE(n_blocks >= 0 && n_blocks <= INT32_MAX - 8 && n_rows >= 0 && n_rows <= INT32_MAX && n_slots >= 0 && row0 >= 0 &&
+                d > 0, "spmm_update_class_tiles: bad shape");
+    REQUIRE(tile_cols > 0 && tile_cols <= d && tiles_share_layout<T>(d, tile_cols),
+            "spmm_update_class_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the "
+            "lane layout (d=%d tile_cols=%d)", d, tile_cols);
+    REQUIRE(items_per_block >= kWavesPerBlock && items_per_block <= kMaxItemsPerBlock,
+            "spmm_update_class_tiles: items_per_block must be in [%d, %d]", kWavesPerBlock, kMaxItemsPerBlock);
+    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_class_tiles: leading dimension < d");
+    const int n_tiles = tile_count(d, tile_cols);
+    REQUIRE(partials_tile_stride >= (n_tiles > 1 ? n_rows : 0), "spmm_update_class_tiles: the tiles' partials overlap");
+    if (n_rows == 0) return CLANE_OK;
+    REQUIRE(colidx && P && item_e0 && item_len && item_slot && class_rows && slot_ptr && Z_old && X && Z_new && slab &&
+                delta_partials, "spmm_update_class_tiles: null pointer");
+    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_class_tiles: Z_new must not alias Z_old");
+    REQUIRE(aligned16(slab), "spmm_update_class_tiles: slab must be 16-byte aligned");
+    const Layout L = pick_layout<T>(tile_cols, {Z_old, X, Z_new}, {ldz, ldx, ldo});
+    REQUIRE(L.vec, "spmm_update_class_tiles: the tables must allow 16-byte packs");
+    const int64_t ld_slab = ceil_div(tile_cols, 8) * 8;
+    const int64_t slab_stride = n_slots * ld_slab;         // clane_spmm_class_slab_len(n_slots, tile_cols) per tile
+    const int chunk_blocks = int(ceil_div(n_blocks, 8) * 8);                 // block 8 j + b of every tile on XCD class b
+    const bool beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
+    REQUIRE(int64_t(n_tiles) * chunk_blocks <= INT32_MAX, "spmm_update_class_tiles: grid too large");
+    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
+        if constexpr (VEC > 1) {
+            constexpr int U = CLANE_LONG_U;
+            constexpr int kDeepU = (LPR == 32 && VEC == 4 && sizeof(T) == 4) ? CLANE_CLASS_U32 : 0;
+            const TileGrid cg{chunk_blocks, tile_cols, 0};
+            const unsigned grid = unsigned(n_tiles) * unsigned(chunk_blocks);
+            if (n_blocks > 0 && kDeepU > 0 && beyond)
+                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, (kDeepU > 0 ? kDeepU : U)>
+                    <<<grid, kBlock, 0, (hipStream_t)stream>>>(colidx, P, item_e0, item_len, item_slot, int(n_blocks),
+                                                               items_per_block, Z_old, ldz, d, slab, ld_slab, slab_stride, cg);
+            else if (n_blocks > 0)
+                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
+                    colidx, P, item_e0, item_len, item_slot, int(n_blocks), items_per_block, Z_old, ldz, d, slab, ld_slab,
+                    slab_stride, cg);
+            const int combine_blocks = int(ceil_div(n_rows, kWave / LPR));
+            const TileGrid bg{combine_blocks, tile_cols, partials_tile_stride};
+            spmm_class_combine_tiles_kernel<T, VEC, LPR>
+                <<<unsigned(n_tiles) * unsigned(combine_blocks), kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
+                    class_rows, slot_ptr, n_rows, row0, slab, ld_slab, slab_stride, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d,
+                    beyond, bg, delta_partials);
+        }
+    });
+    return check_launch("spmm_update_class_tiles");
 }
 
 template <typename T>
@@ -1396,6 +1543,33 @@ int clane_spmm_update_owned_f32(const int32_t *colidx, const float *P, const cla
                                 double *delta_partials, void *stream) {
     return spmm_update_owned<float, float>(colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo,
                                            d, flags, delta_partials, stream);
+}
+int clane_spmm_update_tiles_f32(const int64_t *rowptr, const int32_t *colidx, const float *P, int64_t nrows, int64_t row0,
+                                const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new,
+                                int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold, int32_t flags,
+                                double *delta_partials, int64_t partials_tile_stride, void *stream) {
+    return spmm_update_tiles<float, float>(rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d,
+                                           tile_cols, long_threshold, flags, delta_partials, partials_tile_stride, stream);
+}
+int clane_spmm_update_class_tiles_f32(const int32_t *colidx, const float *P, const int64_t *item_e0,
+                                      const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks,
+                                      int32_t items_per_block, const int32_t *class_rows, const int64_t *slot_ptr,
+                                      int64_t n_rows, int64_t n_slots, int64_t row0, const float *Z_old, int64_t ldz,
+                                      const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                      int32_t tile_cols, int32_t flags, float *slab, double *delta_partials,
+                                      int64_t partials_tile_stride, void *stream) {
+    return spmm_update_class_tiles<float, float>(colidx, P, item_e0, item_len, item_slot, n_blocks, items_per_block,
+                                                 class_rows, slot_ptr, n_rows, n_slots, row0, Z_old, ldz, X, ldx, gamma,
+                                                 Z_new, ldo, d, tile_cols, flags, slab, delta_partials,
+                                                 partials_tile_stride, stream);
+}
+int clane_spmm_update_owned_tiles_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
+                                      int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz,
+                                      const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                      int32_t tile_cols, int32_t flags, double *delta_partials,
+                                      int64_t partials_tile_stride, void *stream) {
+    return spmm_update_owned_tiles<float, float>(colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx, gamma, Z_new,
+                                                 ldo, d, tile_cols, flags, delta_partials, partials_tile_stride, stream);
 }
 int64_t clane_spmm_class_slab_len(int64_t n_slots, int32_t d) { return n_slots * (ceil_div(d, 8) * 8); }
 int64_t clane_spmm_split_slab_len(int64_t n_segments, int32_t d) { return n_segments * (ceil_div(d, 8) * 8); }

@@ -249,12 +249,14 @@ __device__ __forceinline__ void mirror_store_prefetched(const Mirror<T> &mirror,
 
 // MIRRORED: compiled in only for launches that have a mirror (multi-GPU halo / p2p): the prefetched places cost
 // registers (the bf16 sub-wave instance would drop from 5 to 4 waves per SIMD) that a one-GPU sweep must not pay.
+// The work of ONE workgroup of the row pass: rows [block * rows_per_block, ...) of the call, the block's delta partial to
+// *partial.  spmm_update_kernel runs it per blockIdx.x; spmm_update_tiles_kernel runs it per (column tile, block).
 template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
-__global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
+__device__ __forceinline__ void spmm_update_block(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
     typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
-    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, int64_t block, double *__restrict__ partial) {
     using A = typename Elem<T>::acc_t;
     __shared__ int64_t s_rowptr[kMaxRowsPerBlock + 1];
     __shared__ int64_t s_mptr[MIRRORED ? kMaxRowsPerBlock + 1 : 1];   // the block's slice of mirror.row_ptr
@@ -266,7 +268,7 @@ __global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int sub = lane / LPR;
     const int sl = lane % LPR;
-    const int64_t row_begin = int64_t(blockIdx.x) * rows_per_block;
+    const int64_t row_begin = block * rows_per_block;
     const int nb = int((row_begin + rows_per_block < nrows ? row_begin + rows_per_block : nrows) - row_begin);
 
     for (int i = threadIdx.x; i <= nb; i += kBlock) {
@@ -367,7 +369,50 @@ __global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
     double dsum = 0.0;
     for (int i = lane; i < nb; i += kWave) dsum += s_rowsum[i];
     dsum = group_sum<kWave>(dsum);
-    if (lane == 0) partials[blockIdx.x] = dsum;
+    if (lane == 0) *partial = dsum;
+}
+
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+__global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
+    int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
+    typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
+    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    spmm_update_block<T, PT, VEC, LPR, U, MIRRORED>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma, Znew, ldo, d,
+                                                    long_threshold, skip_sinks, rows_per_block, mirror, nt_store,
+                                                    blockIdx.x, partials + blockIdx.x);
+}
+
+// ---- every COLUMN TILE of a pass in one launch ---------------------------------------------------------------------
+// A sweep over column tiles used to launch every kernel once per tile; the in-order stream put a drain and a ramp between
+// the tiles of a pass although nothing orders them (all read Zold, each writes its own columns).  The *_tiles_kernel
+// forms take the WHOLE table and `tile_cols`: workgroup g of a tile-major 1-D grid does what workgroup g % per_tile of
+// tile g / per_tile's own launch did -- the same body on table pointers advanced by the tile's first column, with the
+// tile's width as d and the tile's partials at tile * part_stride -- so the last workgroups of one tile run beside the
+// first of the next.  Bit for bit the per-tile launches.
+struct TileGrid {
+    int per_tile;           // workgroups of one tile
+    int tile_cols;          // columns of every tile but the last, which takes what is left of d
+    int64_t part_stride;    // between the tiles' delta partials
+    __device__ __forceinline__ int tile() const { return int(blockIdx.x) / per_tile; }
+    __device__ __forceinline__ int width(int tile, int d) const {
+        return d - tile * tile_cols < tile_cols ? d - tile * tile_cols : tile_cols;
+    }
+};
+
+template <typename T, typename PT, int VEC, int LPR, int U>
+__global__ CLANE_SPMM_BOUNDS void spmm_update_tiles_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
+    int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
+    typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
+    bool skip_sinks, int rows_per_block, bool nt_store, TileGrid tg, double *__restrict__ partials) {
+    const int tile = tg.tile();
+    const int block = int(blockIdx.x) - tile * tg.per_tile;
+    const int c = tile * tg.tile_cols;
+    spmm_update_block<T, PT, VEC, LPR, U, false>(rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma,
+                                                 Znew + c, ldo, tg.width(tile, d), long_threshold, skip_sinks,
+                                                 rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store, block,
+                                                 partials + tile * tg.part_stride + block);
 }
 
 // Rows that need fewer than 64 lanes (LPR < 64; e.g. d=128 bf16: 16 lanes x 16 B, or the column slices of a
@@ -390,11 +435,11 @@ __global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
 #define CLANE_SUBROW_BOUNDS __launch_bounds__(kBlock)
 #endif
 template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
-__global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_kernel(
+__device__ __forceinline__ void spmm_update_subrow_block(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
     typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
-    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, int64_t block, double *__restrict__ partial) {
     using A = typename Elem<T>::acc_t;
     static_assert(LPR < kWave, "use spmm_update_kernel for rows that fill a wave");
     static_assert(LPR % U == 0, "a sub-wave's edge buffer is consumed in whole groups of U");
@@ -408,7 +453,7 @@ __global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_kernel(
     const int sub = lane / LPR;
     const int sl = lane % LPR;
     const int sub_base = sub * LPR;
-    const int64_t row_begin = int64_t(blockIdx.x) * rows_per_block;
+    const int64_t row_begin = block * rows_per_block;
     const int nb = int((row_begin + rows_per_block < nrows ? row_begin + rows_per_block : nrows) - row_begin);
     const int c0 = sl * VEC;                 // LPR * VEC >= d: a row is one pack per lane
     const bool col_ok = c0 < d;
@@ -530,7 +575,34 @@ __global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_kernel(
     double dsum = 0.0;
     for (int i = lane; i < nb; i += kWave) dsum += s_rowsum[i];
     dsum = group_sum<kWave>(dsum);
-    if (lane == 0) partials[blockIdx.x] = dsum;
+    if (lane == 0) *partial = dsum;
+}
+
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+__global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
+    int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
+    typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
+    bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    spmm_update_subrow_block<T, PT, VEC, LPR, U, MIRRORED>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma, Znew,
+                                                           ldo, d, long_threshold, skip_sinks, rows_per_block, mirror,
+                                                           nt_store, blockIdx.x, partials + blockIdx.x);
+}
+
+// Every column tile of the sub-wave row pass in one launch (see spmm_update_tiles_kernel).
+template <typename T, typename PT, int VEC, int LPR, int U>
+__global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_tiles_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
+    int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
+    typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
+    bool skip_sinks, int rows_per_block, bool nt_store, TileGrid tg, double *__restrict__ partials) {
+    const int tile = tg.tile();
+    const int block = int(blockIdx.x) - tile * tg.per_tile;
+    const int c = tile * tg.tile_cols;
+    spmm_update_subrow_block<T, PT, VEC, LPR, U, false>(rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma,
+                                                        Znew + c, ldo, tg.width(tile, d), long_threshold, skip_sinks,
+                                                        rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store,
+                                                        block, partials + tile * tg.part_stride + block);
 }
 
 // One workgroup of WAVES waves per long row.  Wave w gathers the 64-aligned edge slice w; slices are
@@ -711,10 +783,11 @@ __device__ __forceinline__ Pack<A, VEC> slab_load(const A *p) {
 }
 
 template <typename T, typename PT, int VEC, int LPR, int U>
-__global__ __launch_bounds__(kBlock) void spmm_class_chunk_kernel(
+__device__ __forceinline__ void spmm_class_chunk_block(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
     const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int items_per_block,
-    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab) {
+    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab,
+    int64_t block) {
     using A = typename Elem<T>::acc_t;
     __shared__ int64_t s_e0[kMaxItemsPerBlock];
     __shared__ int s_len[kMaxItemsPerBlock];
@@ -724,7 +797,7 @@ __global__ __launch_bounds__(kBlock) void spmm_class_chunk_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int sub = lane / LPR;
     const int sl = lane % LPR;
-    const int64_t base = int64_t(blockIdx.x) * items_per_block;
+    const int64_t base = block * items_per_block;
     for (int i = threadIdx.x; i < items_per_block; i += kBlock) {
         s_e0[i] = item_e0[base + i];
         s_len[i] = item_len[base + i];
@@ -780,6 +853,32 @@ __global__ __launch_bounds__(kBlock) void spmm_class_chunk_kernel(
     }
 }
 
+template <typename T, typename PT, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void spmm_class_chunk_kernel(
+    const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
+    const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int items_per_block,
+    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab) {
+    spmm_class_chunk_block<T, PT, VEC, LPR, U>(colidx, P, item_e0, item_len, item_slot, items_per_block, Zold, ldz, d,
+                                               slab, ld_slab, blockIdx.x);
+}
+
+// Every column tile's chunks in one launch (see spmm_update_tiles_kernel).  tg.per_tile is the item-block count rounded
+// UP to a multiple of 8, so block 8 j + b of every tile still runs on XCD class b; the workgroups of the padding
+// (block >= n_blocks) return at once.  Tile t's chunk sums live at slab + t * slab_stride: all tiles' at the same time.
+template <typename T, typename PT, int VEC, int LPR, int U>
+__global__ __launch_bounds__(kBlock) void spmm_class_chunk_tiles_kernel(
+    const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
+    const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int n_blocks, int items_per_block,
+    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab,
+    int64_t slab_stride, TileGrid tg) {
+    const int tile = tg.tile();
+    const int block = int(blockIdx.x) - tile * tg.per_tile;
+    if (block >= n_blocks) return;                           // uniform over the workgroup, before any barrier
+    spmm_class_chunk_block<T, PT, VEC, LPR, U>(colidx, P, item_e0, item_len, item_slot, items_per_block,
+                                               Zold + tile * tg.tile_cols, ldz, tg.width(tile, d),
+                                               slab + tile * slab_stride, ld_slab, block);
+}
+
 // One workgroup of kCombineWaves waves per class row.  Wave w adds the w-th contiguous share of the row's slots IN ORDER;
 // wave 0 then adds the waves' sums in wave order (through LDS) and runs the usual epilogue:  z = x + gamma * sum,
 // delta, store.  The association is fixed by (slot count, kCombineWaves) alone -- reproducible, no atomics -- and a
@@ -792,11 +891,11 @@ constexpr int kCombineWaves = CLANE_COMBINE_WAVES;
 constexpr int kCombineLoads = CLANE_COMBINE_LOADS;
 
 template <typename T, int VEC, int LPR>
-__global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_kernel(
+__device__ __forceinline__ void spmm_class_combine_block(
     const int32_t *__restrict__ class_rows, const int64_t *__restrict__ slot_ptr, int64_t n_rows, int64_t row0,
     const typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab, const T *__restrict__ Zold, int64_t ldz,
     const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d,
-    Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    Mirror<T> mirror, bool nt_store, int64_t block, double *__restrict__ partials) {
     using A = typename Elem<T>::acc_t;
     // A row needs LPR lanes; a workgroup takes 64 / LPR rows, one per lane group (round 5: at 512-byte rows -- the column
     // tiles -- half the lanes of the one-row form had nothing to do).  Each group walks its own row's slots: the
@@ -806,7 +905,7 @@ __global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_kerne
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int sub = lane / LPR, sl = lane % LPR;
-    const int64_t i = int64_t(blockIdx.x) * kRows + sub;
+    const int64_t i = block * kRows + sub;
     const bool live = i < n_rows;
     const int64_t r = live ? class_rows[i] : 0;
     const int64_t s0 = live ? slot_ptr[i] : 0, s1 = live ? slot_ptr[i + 1] : 0;
@@ -872,6 +971,32 @@ __global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_kerne
     }
 }
 
+template <typename T, int VEC, int LPR>
+__global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_kernel(
+    const int32_t *__restrict__ class_rows, const int64_t *__restrict__ slot_ptr, int64_t n_rows, int64_t row0,
+    const typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab, const T *__restrict__ Zold, int64_t ldz,
+    const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d,
+    Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
+    spmm_class_combine_block<T, VEC, LPR>(class_rows, slot_ptr, n_rows, row0, slab, ld_slab, Zold, ldz, X, ldx, gamma,
+                                          Znew, ldo, d, mirror, nt_store, blockIdx.x, partials);
+}
+
+// Every column tile's combine in one launch (see spmm_update_tiles_kernel): tile t reads the slab at t * slab_stride.
+template <typename T, int VEC, int LPR>
+__global__ __launch_bounds__(kCombineWaves *kWave) void spmm_class_combine_tiles_kernel(
+    const int32_t *__restrict__ class_rows, const int64_t *__restrict__ slot_ptr, int64_t n_rows, int64_t row0,
+    const typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab, int64_t slab_stride, const T *__restrict__ Zold,
+    int64_t ldz, const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo,
+    int d, bool nt_store, TileGrid tg, double *__restrict__ partials) {
+    const int tile = tg.tile();
+    const int block = int(blockIdx.x) - tile * tg.per_tile;
+    const int c = tile * tg.tile_cols;
+    spmm_class_combine_block<T, VEC, LPR>(class_rows, slot_ptr, n_rows, row0, slab + tile * slab_stride, ld_slab, Zold + c,
+                                          ldz, X + c, ldx, gamma, Znew + c, ldo, tg.width(tile, d),
+                                          Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store, block,
+                                          partials + tile * tg.part_stride);
+}
+
 // ---- owned class rows: the sums never leave the CU ---------------------------------------------------------------
 // The chunk + combine pair above sends every partial sum of a class row through HBM (the slab) because the row's
 // chunks run on eight XCDs.  Here the XCD-private L2s get their disjoint working sets in TIME instead of in space: a
@@ -914,9 +1039,10 @@ template <typename T, typename PT, int VEC, int LPR, int U>
 __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, OwnedPlan plan, int64_t row0,
     const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma,
-    T *__restrict__ Znew, int64_t ldo, int d, bool nt_store, double *__restrict__ partials) {
+    T *__restrict__ Znew, int64_t ldo, int d_left, int tile_cols, int64_t part_stride, bool ahead, bool nt_store,
+    double *__restrict__ partials) {
     using A = typename Elem<T>::acc_t;
-    constexpr int W = LPR * VEC;            // elements of one LDS sum: the whole row (the host checks d <= W)
+    constexpr int W = LPR * VEC;            // elements of one LDS sum: the whole tile row (the host checks tile_cols <= W)
     constexpr int kRows = kWave / LPR;      // rows finished by one wave at a time
     extern __shared__ __align__(16) unsigned char s_owned_raw[];
     A *s_sum = reinterpret_cast<A *>(s_owned_raw);
@@ -927,12 +1053,17 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
     const int nwaves = int(blockDim.x) / kWave;
     const int sub = lane / LPR, sl = lane % LPR;
     const int c0 = sl * VEC;
-    const bool col_ok = c0 < d;
-    const T *zcol = Zold + (col_ok ? c0 : 0);
     const int n_steps = plan.n_steps;
     const int64_t chunk = plan.chunk;
     const int b0 = plan.grp_bat_ptr[blockIdx.x], b1 = plan.grp_bat_ptr[blockIdx.x + 1];
 
+    // The column tiles of the table, one after the other inside the persistent workgroup (the per-tile call: one tile of
+    // all d_left columns): the same plan, sums and steps per tile; the table pointers move on by tile_cols columns and
+    // the delta partials by part_stride from tile to tile.
+    for (; d_left > 0; d_left -= tile_cols, Zold += tile_cols, X += tile_cols, Znew += tile_cols, partials += part_stride) {
+    const int d = d_left < tile_cols ? d_left : tile_cols;
+    const bool col_ok = c0 < d;
+    const T *zcol = Zold + (col_ok ? c0 : 0);
     for (int b = b0; b < b1; ++b) {                          // uniform over the workgroup
         const int v0 = plan.bat_vrow_ptr[b];
         const int nv = plan.bat_vrow_ptr[b + 1] - v0;
@@ -994,6 +1125,64 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
         // the batch's rows: virtual rows added in order, then  z = x + gamma * sum,  delta, store
         const int r0 = plan.bat_row_ptr[b];
         const int nr = plan.bat_row_ptr[b + 1] - r0;
+        if (ahead) {
+            // No gather is in flight here, and a trip of the plain loop below is a chain of dependent round trips: the
+            // row's ids, then its x / z_old, then the store.  With `ahead` a wave requests the ids of the row group TWO
+            // trips on and the x / z_old of the NEXT one before it finishes the current group, so what it finishes has
+            // arrived under the trips before.  The same loads, sums and stores per row: not a bit changes.
+            struct RowIds {
+                int r, va, vb, part;
+                bool live;
+            };
+            const int stride = nwaves * kRows;
+            auto ids_of = [&](int j0) -> RowIds {
+                RowIds m{0, 0, 0, 0, false};
+                const int j = j0 + sub;
+                if (j0 < nr && j < nr) {
+                    m.r = plan.row_id[r0 + j];
+                    m.va = plan.row_vptr[r0 + j] - v0;
+                    m.vb = plan.row_vptr[r0 + j + 1] - v0;
+                    m.part = plan.row_part[r0 + j];
+                    m.live = true;
+                }
+                return m;
+            };
+            auto request = [&](const RowIds &m, Pack<T, VEC> &x, Pack<T, VEC> &zo) {
+                if (m.live && col_ok) {
+                    x = load_pack_stream<T, VEC>(X + int64_t(m.r) * ldx + c0);
+                    zo = load_pack_stream<T, VEC>(Zold + (row0 + m.r) * ldz + c0);
+                }
+            };
+            int j0 = wave * kRows;
+            RowIds cur = ids_of(j0), nxt = ids_of(j0 + stride);
+            Pack<T, VEC> x{}, zo{};
+            request(cur, x, zo);
+            for (; j0 < nr; j0 += stride) {                                  // uniform over the wave
+                const RowIds far = ids_of(j0 + 2 * stride);
+                Pack<T, VEC> xn{}, zon{};
+                request(nxt, xn, zon);
+                A rsum = A(0);
+                if (cur.live && col_ok) {
+                    A acc[VEC];
+                    const Pack<A, VEC> first = load_pack<A, VEC>(s_sum + cur.va * W + c0);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] = first.v[k];
+                    for (int v = cur.va + 1; v < cur.vb; ++v) {
+                        const Pack<A, VEC> t = load_pack<A, VEC>(s_sum + v * W + c0);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) acc[k] += t.v[k];
+                    }
+                    Pack<T, VEC> out{};
+                    rsum = finish_pack<T, VEC>(x, zo, acc, gamma, true, Znew + int64_t(cur.r) * ldo + c0, out, nt_store);
+                }
+                rsum = group_sum<LPR>(rsum);
+                if (cur.live && sl == 0) partials[cur.part] = double(rsum);
+                cur = nxt;
+                nxt = far;
+                x = xn;
+                zo = zon;
+            }
+        } else
         for (int j0 = wave * kRows; j0 < nr; j0 += nwaves * kRows) {     // uniform over the wave
             const int j = j0 + sub;
             const bool live = j < nr;
@@ -1020,6 +1209,7 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
             if (live && sl == 0) partials[plan.row_part[r0 + j]] = double(rsum);
         }
         __syncthreads();                                      // the sums are read: the next batch may zero them
+    }
     }
 }
 

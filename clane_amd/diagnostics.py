@@ -48,13 +48,15 @@ class DiagnosticsMixin:
                 "hub": int(per_row[is_hub].sum()), "split": int(per_row[is_split | is_class].sum())}
 
     def launches_per_sweep(self) -> int:
-        """Launches of each K3 kernel per sweep: one per launch block and column tile."""
-        return len(self.blocks) * len(self.tiles)
+        """Launches of each K3 kernel per sweep: one per launch block and column tile (per block where the passes run
+        all tiles in one launch)."""
+        return len(self.blocks) * (1 if getattr(self, "fused_tiles", None) else len(self.tiles))
 
     def kernel_names(self):
         """Names of the K3 kernels behind the keys of kernel_times_ms() / kernel_bytes()."""
         narrow = self.d > 0 and lanes_per_row(self.d_plan if len(self.tiles) > 1 else self.d, self.dtype) < 64
-        return {"main": "spmm_update_subrow_kernel" if narrow else "spmm_update_kernel",
+        fused = getattr(self, "fused_tiles", frozenset())      # the passes that run all column tiles in one launch
+        return {"main": ("spmm_update_subrow" if narrow else "spmm_update") + ("_tiles_kernel" if "row" in fused else "_kernel"),
                 "mid": "spmm_long_kernel<4 waves>", "hub": "spmm_long_kernel<16 waves>",
                 "split": ("spmm_owned_kernel+spmm_class_chunk_kernel+combine" if getattr(self, "class_owned", False)
                           else "spmm_class_chunk_kernel+combine") if self.class_threshold > 0
@@ -95,6 +97,10 @@ class DiagnosticsMixin:
                                     "batch_vrows": self.owned_batch_vrows, "chunk": self.owned_chunk,
                                     "loads": self.owned_loads}}
                    if getattr(self, "class_owned", False) else {}),
+                # only where a pass runs all column tiles in one launch (and the owned epilogue looks ahead)
+                **({"fused_tiles": sorted(self.fused_tiles)} if getattr(self, "fused_tiles", None) else {}),
+                **({"owned_ahead": True} if getattr(self, "class_owned", False) and getattr(self, "owned_ahead", False)
+                   else {}),
                 }
 
     def exchange_bytes_per_sweep(self) -> int:

@@ -31,7 +31,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _hip, owned, xcd
+from . import _hip, fused, owned, xcd
 from .blocks import BlockRows, ClassItems, PartialLayout, SplitRows
 from .comm import TorchComm
 from .diagnostics import DiagnosticsMixin
@@ -70,7 +70,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                  owned_max_edges: int = xcd.OWNED_MAX_EDGES, owned_row_edges: int = xcd.OWNED_ROW_EDGES,
                  owned_groups: int = xcd.OWNED_GROUPS, owned_lds_bytes: int = xcd.OWNED_LDS_BYTES,
                  owned_block_threads: int = xcd.OWNED_BLOCK_THREADS, owned_chunk: Optional[int] = None,
-                 owned_loads: int = xcd.OWNED_LOADS):
+                 owned_loads: int = xcd.OWNED_LOADS, owned_ahead: Optional[bool] = None, fused_tiles=None):
         """``exchange`` (N > 1 only) -- how the sweep is divided over the GPUs:
         "auto" (default) -- "columns" while a rank's slice of a row is >= 64 bytes, else "halo" (pick_exchange).
         "columns" -- every GPU holds the whole graph and d/N COLUMNS of X and Z.  ``Z[:, c] = X[:, c] + gamma P Z[:, c]``
@@ -89,7 +89,13 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         are cut into virtual rows; ``owned_groups`` workgroups of ``owned_block_threads`` threads, each with
         ``owned_lds_bytes`` of LDS for its sums; ``owned_chunk``: piece length (None = ``class_chunk``); ``owned_loads``: row
         loads in flight per wave (0 = as the chunk kernel).  Results depend on ``owned_max_edges``, ``owned_row_edges``
-        and ``owned_chunk`` alone.
+        and ``owned_chunk`` alone.  ``owned_ahead``: the owned epilogue requests the next rows' x / z_old before it
+        finishes the current ones (None = xcd.OWNED_EPILOGUE_AHEAD where the backend has it).
+        ``fused_tiles`` -- with column tiles, ONE launch per pass for all tiles (spmm_update*_tiles) instead of one per
+        tile: None = the passes of xcd.FUSED_TILES_DEFAULT, True = every pass, False = none, or the passes by name
+        ("row", "class", "owned").  Taken only with more than one tile, uniform tiles (tile t is columns
+        [t x width, (t + 1) x width)), fp32 tables, no mirrors and a backend that has the calls; every other engine
+        keeps the per-tile plan.  Bit for bit the same either way.
         The constructor is a sequence of steps, each a method: the division over the ranks, the class-pass thresholds,
         the row layout, the row bins, the structure upload, the launch lists, the exchange lists, the tables, scratch."""
         if X.dim() != 2 or X.shape[0] != csr.num_vertices:
@@ -113,6 +119,9 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self._choose_owned(class_owned, owned_max_edges, owned_row_edges, owned_groups, owned_lds_bytes,
                            owned_block_threads, owned_chunk)
         self.owned_loads = int(owned_loads)
+        ahead = xcd.OWNED_EPILOGUE_AHEAD if owned_ahead is None else bool(owned_ahead)
+        self.owned_ahead = bool(ahead and self.k.owned_epilogue_ahead)
+        self._choose_fused_tiles(fused_tiles)
         self._build_layout(csr, chunks, shuffle, seed, hot_rows_first)
         self._choose_row_bins(long_threshold, hub_threshold)
         deg = self._upload_structure()
@@ -251,6 +260,37 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         self.owned_chunk = int(chunk) if chunk is not None else self.class_chunk
         if self.class_owned:
             self._check_owned_settings()
+
+    FUSED_PASSES = ("row", "class", "owned")
+
+    def _choose_fused_tiles(self, asked) -> None:
+        """Which passes run all column tiles in one launch: `fused_possible`, and `fused_tiles`, a frozenset of FUSED_PASSES
+        (empty wherever the fused calls do not apply: the engine then keeps one launch per tile)."""
+        w = self.tiles[0][1] - self.tiles[0][0]
+        uniform = all(c0 == t * w and c1 == c0 + w for t, (c0, c1) in enumerate(self.tiles))     # the cuts are even or not
+        self.fused_possible = bool(len(self.tiles) > 1 and uniform and self.world == 1 and not self._forced
+                                   and self.dtype == torch.float32
+                                   and fused.backend_has(self, w))
+        if asked is None:
+            want = xcd.FUSED_TILES_DEFAULT
+        elif isinstance(asked, bool):
+            want = self.FUSED_PASSES if asked else ()
+        else:
+            want = tuple(asked)
+            if any(p not in self.FUSED_PASSES for p in want):
+                raise ValueError(f"fused_tiles: passes are {self.FUSED_PASSES}, got {asked!r}")
+        self.fused_tiles = frozenset(want) if self.fused_possible else frozenset()
+
+    def set_fused_tiles(self, on, ahead: Optional[bool] = None) -> None:
+        """Switch the fused launches (True / False / passes by name, as the constructor's ``fused_tiles``) and the owned
+        epilogue's look-ahead between sweeps: for A/B timings on ONE engine's tables (tools/fused_tiles_ab.py).  An engine
+        the fused calls do not apply to stays on the per-tile plan whatever is asked."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self._choose_fused_tiles(on)
+        if ahead is not None:
+            self.owned_ahead = bool(ahead and self.k.owned_epilogue_ahead)
+        self._plans = {}
 
     def _check_owned_settings(self) -> None:
         widths = [c1 - c0 for c0, c1 in self.tiles]
@@ -399,7 +439,9 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         # segment sums of the split hub rows: one slab per launch stream (blocks on a stream run in order)
         slab_len = max(1, self.k.spmm_split_slab_len(max_segments, max(self.d_plan, 1)))
         if max_slots:
-            slab_len = max(slab_len, self.k.spmm_class_slab_len(max_slots, max(self.d_plan, 1)), 2 * max_slots)   # K1: 2 stats per slot
+            # with fused tiles every tile's chunk sums live at the same time (set_fused_tiles may switch them on later)
+            slab_len = max(slab_len, (len(self.tiles) if self.fused_possible else 1)
+                           * self.k.spmm_class_slab_len(max_slots, max(self.d_plan, 1)), 2 * max_slots)   # K1: 2 stats per slot
         # one slab per launch stream: blocks alternate between two side streams when there are several
         self.slabs = [torch.zeros(slab_len, dtype=self.acc_dtype, device=dev)
                       for _ in range(2 if len(self.blocks) > 1 else 1)]
@@ -824,19 +866,32 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 if mir is not None and T > 1:
                     raise AssertionError("column tiles and mirrored launches do not combine")
 
+                # FUSED passes: one call over the whole tables for all tiles (spmm_update*_tiles); tile t's partials
+                # follow tile 0's at t x the length of a tile's partials, exactly where `part` puts them
+                on = self.fused_tiles if (T > 1 and mir is None) else frozenset()
+                tile_cols, stride, slab = width(0), partial_off[-1], self.slabs[i % len(self.slabs)]
+
+                def class_launch_tiles(items):      # chunk + combine over `items` for every tile: two launches
+                    return ("call", fused.bind_class(self, items, b.row0, Zold, Xb, gamma, Zn, tile_cols, slab,
+                                                     part(lay.klass, 0), stride))
+
                 def class_launch(items, t):         # chunk + combine over `items` (a ClassItems) of this block
                     return ("call", self._bind("spmm_update_class", self.colidx, self.P, items.e0, items.len, items.slot,
                                                items.items_per_block, items.rows, items.slot_ptr, b.row0, cut(Zold, t),
                                                cut(Xb, t), gamma, cut(Zn, t), width(t), self.slabs[i % len(self.slabs)],
                                                part(lay.klass, t), mirror=mir, beyond_cache=self.beyond_cache))
+                if rows.owned is not None and "owned" in on:
+                    steps.append(("call", owned.bind_launch_tiles(self, rows.owned.plan, b.row0, Zold, Xb, gamma, Zn,
+                                                                  tile_cols, part(lay.klass, 0), stride)))
+                klass = rows.klass if rows.owned is None else rows.owned.rest
+                if klass is not None and "class" in on:
+                    steps.append(class_launch_tiles(klass))
                 for t in range(T):
-                    if rows.owned is not None:      # the owned rows in LDS, the rows above them by chunk + combine
+                    if rows.owned is not None and "owned" not in on:   # the owned rows in LDS,
                         steps.append(("call", owned.bind_launch(self, rows.owned.plan, b.row0, cut(Zold, t), cut(Xb, t),
                                                                 gamma, cut(Zn, t), width(t), part(lay.klass, t))))
-                        if rows.owned.rest is not None:
-                            steps.append(class_launch(rows.owned.rest, t))
-                    elif rows.klass is not None:
-                        steps.append(class_launch(rows.klass, t))
+                    if klass is not None and "class" not in on:        # the rows above them by chunk + combine
+                        steps.append(class_launch(klass, t))
                     if rows.split is not None:
                         steps.append(("call", self._bind("spmm_update_split", rp, self.colidx, self.P, rows.split.rows,
                                                          rows.split.seg_ptr, rows.split.seg_row, self.segment_edges, b.row0,
@@ -855,7 +910,10 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                                                          b.row0, cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
                                                          part(lay.mid, t), mirror=mir)))
                 steps.append(("event", i, 2))
-                for t in range(T):
+                if "row" in on:
+                    steps.append(("call", fused.bind_row(self, rp, b.nrows, b.row0, Zold, Xb, gamma, Zn, tile_cols,
+                                                         part(lay.main, 0), stride)))
+                for t in range(T if "row" not in on else 0):
                     steps.append(("call", self._bind("spmm_update", rp, self.colidx, self.P, b.nrows, b.row0, cut(Zold, t),
                                                      cut(Xb, t), gamma, cut(Zn, t), width(t), self.long_threshold,
                                                      part(lay.main, t), sinks_untouched=True, mirror=mir,

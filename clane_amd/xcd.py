@@ -237,6 +237,12 @@ OWNED_LOADS = 12                 # row loads in flight per wave (CLANE_OWNED_LOA
 # Infinity Cache (engine.beyond_cache), where the kernel has an instance.  A cache-resident table (config 2) or evenly
 # spread reads keep chunk + combine: not measured to gain, so not switched.
 OWNED_DEFAULT = True
+# SweepEngine(fused_tiles=None): the passes that run ALL column tiles in one launch (spmm_update*_tiles: "row", "class",
+# "owned") instead of one launch per tile, and SweepEngine(owned_ahead=None): whether the owned epilogue requests the next
+# rows' x / z_old ahead.  Bit for bit the per-tile plan; each piece is on where its own pass's time fell by more than
+# the box's spread (profiles/r16_fused_tiles.md), else off.
+FUSED_TILES_DEFAULT = ("row", "class", "owned")
+OWNED_EPILOGUE_AHEAD = True
 
 
 def owned_plan(sizes: np.ndarray, seg_len: np.ndarray, seg_e0: np.ndarray, row_ids: np.ndarray, row_parts: np.ndarray,

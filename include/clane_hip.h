@@ -70,7 +70,10 @@ extern "C" {
                              *    no combine pass; embedder.py:90-92)
                              *    + clane_csr_spmm_f32, clane_csr_row_sums_f32, clane_csr_spmm_segment, clane_csr_spmm_ws_len
                              *    (sparse content: CSR rows times a dense matrix with a rank-one epilogue and the rows'
-                             *    value sums -- the products of a randomized PCA on a bag of words) */
+                             *    value sums -- the products of a randomized PCA on a bag of words)
+                             *    + clane_spmm_update_tiles_f32, clane_spmm_update_class_tiles_f32,
+                             *    clane_spmm_update_owned_tiles_f32 (every column tile of a K3 pass in ONE launch, bit for
+                             *    bit the per-tile calls) and the flag CLANE_OWNED_EPILOGUE_AHEAD of the owned calls */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -378,6 +381,9 @@ int clane_spmm_update_class_bf16(const int32_t *colidx, const float *P, const in
  *                             per wave (6, 8, 12 up to d = 128; 8, 12 above; 0 = the chunk kernel's choice).  Neither
  *                             changes a result. */
 #define CLANE_OWNED_LOADS(n) (((n) & 0xff) << 8)
+/* flag of the owned calls: a wave requests x / z_old of the next row group (and the ids of the one after) before it
+ * finishes the current one, instead of one chain of dependent loads per group.  Changes no result. */
+#define CLANE_OWNED_EPILOGUE_AHEAD (1 << 16)
 typedef struct {
     const int32_t *grp_bat_ptr;
     const int32_t *bat_vrow_ptr;
@@ -398,6 +404,42 @@ int clane_spmm_update_owned_f32(const int32_t *colidx, const float *P, const cla
                                 int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz, const float *X,
                                 int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d, int32_t flags,
                                 double *delta_partials, void *stream);
+
+/*  Every COLUMN TILE of a K3 pass in one launch (fp32, no mirror).  A sweep may be run as passes over column tiles of
+ *  the same tables (the update is independent per column, embedder.py:92); calling clane_spmm_update_f32 /
+ *  _class_f32 / _owned_f32 once per tile puts a drain and a ramp between the tiles of a pass on an in-order stream,
+ *  although nothing orders them.  These take the WHOLE table (d columns) and `tile_cols`: tile t covers columns
+ *  [t tile_cols, min(d, (t + 1) tile_cols)) -- the last may be narrower -- and is computed exactly as the per-tile call on
+ *  (Z_old + t tile_cols, X + t tile_cols, Z_new + t tile_cols, width of the tile) computes it, with the kernel
+ *  instance of a full tile's width and the flags; tile t's delta partials start at
+ *  delta_partials + t * partials_tile_stride and are laid out as the per-tile call lays them out.  Bit for bit the
+ *  per-tile calls: Z_new, every partial.  tile_cols must be a multiple of 4 (16-byte packs), Z_old / X / Z_new must
+ *  allow 16-byte packs, and the last tile must take the lane layout of a full one (8 / 16 / 32 / 64 lanes for up to
+ *  32 / 64 / 128 / more columns); anything else is CLANE_ERR_INVALID_ARGUMENT -- the caller keeps the per-tile calls.
+ *   clane_spmm_update_tiles_f32        the row pass: a 1-D grid of tiles x workgroups, tile-major.
+ *   clane_spmm_update_class_tiles_f32  chunk + combine, each ONE launch over all tiles.  The chunk grid is tiles x
+ *                                      (n_blocks rounded up to a multiple of 8), so item block 8 j + b of every tile
+ *                                      runs on XCD class b; n_slots = slot_ptr[n_rows]; tile t's chunk sums live at
+ *                                      slab + t * clane_spmm_class_slab_len(n_slots, tile_cols): slab holds
+ *                                      tiles * that many elements.
+ *   clane_spmm_update_owned_tiles_f32  the persistent workgroups walk the tiles one after the other: the same plan, LDS
+ *                                      sums (sized by tile_cols) and steps per tile. */
+int clane_spmm_update_tiles_f32(const int64_t *rowptr, const int32_t *colidx, const float *P, int64_t nrows, int64_t row0,
+                                const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new,
+                                int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold, int32_t flags,
+                                double *delta_partials, int64_t partials_tile_stride, void *stream);
+int clane_spmm_update_class_tiles_f32(const int32_t *colidx, const float *P, const int64_t *item_e0,
+                                      const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks,
+                                      int32_t items_per_block, const int32_t *class_rows, const int64_t *slot_ptr,
+                                      int64_t n_rows, int64_t n_slots, int64_t row0, const float *Z_old, int64_t ldz,
+                                      const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                      int32_t tile_cols, int32_t flags, float *slab, double *delta_partials,
+                                      int64_t partials_tile_stride, void *stream);
+int clane_spmm_update_owned_tiles_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
+                                      int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz,
+                                      const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                      int32_t tile_cols, int32_t flags, double *delta_partials,
+                                      int64_t partials_tile_stride, void *stream);
 
 /* out[0] = sum of partials[0..n) in a fixed order (bitwise reproducible).  Finishes embedder.py:94 / :60.
  * ws: clane_reduce_ws_len() doubles. */
