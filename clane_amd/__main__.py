@@ -111,6 +111,13 @@ def embedding(args):
         if not arrivals_root.is_absolute():
             arrivals_root = Path(args.data_root) / arrivals_root
         arrivals = induct.read_arrivals(arrivals_root, read_vertex_ids(Path(args.data_root)), None)
+    # optional section (extension): layout: {perplexity: 30, max_points: 20000, max_iter: 1000, seed: 0, labels: Y,
+    # baseline: true} -- the 2-D t-SNE picture of the embeddings the run ends with (layout.py); checked before the graph loads
+    layout_cfg = layout_labels = None
+    if isinstance(hparams, dict) and "layout" in hparams:
+        from . import layout as layout_mod
+        layout_cfg = layout_mod.check_section(hparams["layout"], int(os.environ.get("WORLD_SIZE", "1")))
+        layout_labels = layout_mod.resolve_labels(layout_cfg, Path(args.data_root))
 
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
@@ -309,6 +316,16 @@ def embedding(args):
                     io.write(f"{g.vertex_ids[v]}\t{c}\n")
         say(f"The clustering of {first['clustered']} vertices into {first['clusters']} clusters is stored in "
             f"{out.absolute()}.")
+
+    if layout_cfg is not None:                      # the picture of the embeddings the run ends with
+        from . import layout as layout_mod
+        kw = {key: layout_cfg[key] for key in ("perplexity", "max_points", "max_iter", "seed")}
+        tables = {"Z": g.layout(table="Z", labels=layout_labels, **kw)}
+        if layout_cfg["baseline"]:
+            tables["X"] = g.layout(table="X", labels=layout_labels, **kw)
+        report = layout_mod.write_results(args.output_root, g.vertex_ids, tables)
+        say(f"The 2-D layout of {report['n']} vertices ({report['iterations']} iterations, KL {report['kl']:.4f}) is "
+            f"stored in {args.output_root.joinpath('layout.tsv').absolute()}.")
 
     if arrivals is not None:                        # with the similarity the run ends with: trained weights included
         from . import induct

@@ -144,6 +144,16 @@ SIGNATURES["clane_csr_spmm_ws_len"] = (_i64, [_i64, _i64, _i32])
 SIGNATURES["clane_csr_spmm_f32"] = (
     C.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _p])
 SIGNATURES["clane_csr_row_sums_f32"] = (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _p, _p])
+TSNE_MAX_POINTS = 65536             # CLANE_TSNE_MAX_POINTS; 2-D layout (csrc/tsne.h)
+TSNE_FORCES_KL, TSNE_FORCES_CACHED = 1, 2
+for _s in ("f32", "bf16"):
+    SIGNATURES[f"clane_tsne_sqdist_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _p, _p])
+SIGNATURES["clane_tsne_affinities_f32"] = (C.c_int, [_p, _i64, C.c_float, _p, _p])
+SIGNATURES["clane_tsne_symmetrize_ws_len"] = (_i64, [_i64])
+SIGNATURES["clane_tsne_symmetrize_f32"] = (C.c_int, [_p, _i64, _p, _p])
+SIGNATURES["clane_tsne_forces_f32"] = (C.c_int, [_p, _p, _i64, _i32, _p, _p])
+SIGNATURES["clane_tsne_step_f32"] = (
+    C.c_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p])
 
 
 def probe_padded_classes(C_: int) -> int:
@@ -604,6 +614,32 @@ class KernelBackend(abc.ABC):
     def csr_row_sums(self, S, sums, ws=None):
         """sums[r] (float64) = the sum of the values of row r, in a fixed order."""
         raise NotImplementedError(f"{type(self).__name__} has no csr_row_sums")
+
+    # 2-D layout (layout.py): optional in the same way -- TSNE is the only caller.  D / P [n, n], Y / V / G [n, 2], F [n, 6]
+    # float32 and contiguous; everything but sqdist's table is float32 whatever the table's dtype.
+    def tsne_sqdist(self, Z, d: int, rows, mu, sq, D):
+        """D[i, j] = max(0, |a_i|^2 + |a_j|^2 - 2 a_i . a_j) with a = Z[rows, :d] - mu (a row outside the table: z = 0);
+        bitwise symmetric, the diagonal exactly 0; sq [n]: the squared norms, a workspace."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_sqdist")
+
+    def tsne_affinities(self, D, perplexity: float, beta):
+        """In place: row i of D becomes the conditional affinities p_{j|i} at the beta_i of the given perplexity."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_affinities")
+
+    def tsne_symmetrize_ws_len(self, n: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_symmetrize_ws_len")
+
+    def tsne_symmetrize(self, P, partials):
+        """In place: P = max((P + P^T) / 2n, 2.220446e-16), 0 on the diagonal; partials: sum p ln p per tile pair."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_symmetrize")
+
+    def tsne_forces(self, P, Y, F, kl: bool = True, cached: bool = False):
+        """F[i] = (attraction x, y; repulsion x, y; sum_{j != i} q_ij; with ``kl`` sum_j P_ij log1p(|y_i - y_j|^2))."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_forces")
+
+    def tsne_step(self, F, Y, alpha: float, momentum: float, lr: float, plogp: float, V, G, Y_next, stats):
+        """scikit-learn's gradient-descent update from the force sums; stats (float64 [4]) = KL, |g|, S, sum l."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_step")
 
     # owned class rows (csrc/spmm_update.h, spmm_owned_kernel): optional in the same way -- a backend without them keeps
     # every class row on spmm_update_class, and SweepEngine asks `has_spmm_owned` before it plans for them
@@ -1419,6 +1455,68 @@ class HipKernels(KernelBackend):
                      _ptr(long_rows), _ptr(seg_ptr), _ptr(item_long), long_rows.numel(), n_items,
                      None if not n_items else _vec(ws, torch.float64, "ws"), 0 if not n_items else ws.numel(),
                      _vec(sums, torch.float64, "sums"), self._stream(sums))
+
+    # -- 2-D layout ---------------------------------------------------------------------------
+    @staticmethod
+    def _tsne_square(M, what: str) -> int:
+        if M.dim() != 2 or M.shape[0] != M.shape[1] or M.dtype != torch.float32 or not M.is_contiguous():
+            raise ValueError(f"{what}: need a contiguous float32 [n, n] matrix, got {tuple(M.shape)} {M.dtype}")
+        return int(M.shape[0])
+
+    def tsne_sqdist(self, Z, d: int, rows, mu, sq, D):
+        zp, ldz = _mat(Z, "Z")
+        if Z.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"tsne_sqdist: float32 and bfloat16 tables, not {Z.dtype}")
+        n = self._tsne_square(D, "tsne_sqdist")
+        if rows.numel() != n or mu.numel() != d or sq.numel() != n:
+            raise ValueError(f"tsne_sqdist: D must be [n, n] for the n = {rows.numel()} rows, mu [{d}], sq [n]")
+        f32 = torch.float32
+        self._invoke(self._fn("clane_tsne_sqdist", Z.dtype), "clane_tsne_sqdist",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(mu, f32, "mu"), _vec(sq, f32, "sq"),
+                     D.data_ptr(), self._stream(D))
+
+    def tsne_affinities(self, D, perplexity: float, beta):
+        n = self._tsne_square(D, "tsne_affinities")
+        if beta.numel() != n:
+            raise ValueError(f"tsne_affinities: beta needs {n} entries")
+        self._invoke(self.lib.clane_tsne_affinities_f32, "clane_tsne_affinities",
+                     D.data_ptr(), n, float(perplexity), _vec(beta, torch.float32, "beta"), self._stream(D))
+
+    def tsne_symmetrize_ws_len(self, n: int) -> int:
+        return int(self.lib.clane_tsne_symmetrize_ws_len(n))
+
+    def tsne_symmetrize(self, P, partials):
+        n = self._tsne_square(P, "tsne_symmetrize")
+        if partials.numel() != self.tsne_symmetrize_ws_len(n):
+            raise ValueError("tsne_symmetrize: partials needs tsne_symmetrize_ws_len(n) doubles")
+        self._invoke(self.lib.clane_tsne_symmetrize_f32, "clane_tsne_symmetrize",
+                     P.data_ptr(), n, _vec(partials, torch.float64, "partials"), self._stream(P))
+
+    @staticmethod
+    def _tsne_points(n: int, what: str, **arrays):
+        for name, t in arrays.items():
+            cols = 6 if name == "F" else 2
+            if tuple(t.shape) != (n, cols):
+                raise ValueError(f"{what}: {name} must be [{n}, {cols}], got {tuple(t.shape)}")
+
+    def tsne_forces(self, P, Y, F, kl: bool = True, cached: bool = False):
+        n = self._tsne_square(P, "tsne_forces")
+        self._tsne_points(n, "tsne_forces", Y=Y, F=F)
+        f32 = torch.float32
+        self._invoke(self.lib.clane_tsne_forces_f32, "clane_tsne_forces",
+                     P.data_ptr(), _vec(Y, f32, "Y"), n, (TSNE_FORCES_KL if kl else 0) | (TSNE_FORCES_CACHED if cached else 0),
+                     _vec(F, f32, "F"), self._stream(P))
+
+    def tsne_step(self, F, Y, alpha: float, momentum: float, lr: float, plogp: float, V, G, Y_next, stats):
+        n = int(Y.shape[0])
+        self._tsne_points(n, "tsne_step", F=F, Y=Y, V=V, G=G, Y_next=Y_next)
+        if stats.numel() != 4:
+            raise ValueError("tsne_step: stats needs 4 doubles")
+        f32 = torch.float32
+        self._invoke(self.lib.clane_tsne_step_f32, "clane_tsne_step",
+                     _vec(F, f32, "F"), _vec(Y, f32, "Y"), n, float(alpha), float(momentum), float(lr), float(plogp),
+                     _vec(V, f32, "V"), _vec(G, f32, "G"), _vec(Y_next, f32, "Y_next"), _vec(stats, torch.float64, "stats"),
+                     self._stream(Y))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

@@ -23,6 +23,7 @@
 #include "projection.h"
 #include "sparse_rows.h"
 #include "spmm_update.h"
+#include "tsne.h"
 
 namespace {
 
@@ -1233,6 +1234,26 @@ int project_affine(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const
     return check_launch("project_affine");
 }
 
+// ---- 2-D layout (tsne.h) ------------------------------------------------------------------------------------------------
+inline int64_t tsne_sym_tiles(int64_t n) { return ceil_div(n > 0 ? n : 1, int64_t(kTsneSymTile)); }
+
+template <typename T>
+int tsne_sqdist(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const float *mu,
+                float *sq, float *D, void *stream) {
+    static_assert(kTsneMaxPoints == CLANE_TSNE_MAX_POINTS, "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && n <= kTsneMaxPoints && d > 0 && ldz >= d,
+            "tsne_sqdist: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    if (n == 0) return CLANE_OK;
+    REQUIRE(rows && mu && sq && D && (Z || table_rows == 0), "tsne_sqdist: null pointer");
+    const int64_t nt = ceil_div(n, int64_t(kProjBM));
+    tsne_sqnorm_kernel<T><<<unsigned(ceil_div(n, int64_t(kBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, rows, n, mu, sq);
+    tsne_sqdist_kernel<T><<<unsigned(nt * (nt + 1) / 2), kBlock, 0, (hipStream_t)stream>>>(Z, table_rows, d, ldz, rows, n,
+                                                                                           mu, sq, D, int(nt));
+    return check_launch("tsne_sqdist");
+}
+
 // ---- sparse rows (sparse_rows.h) ----------------------------------------------------------------------------------------
 inline int64_t csr_max_items(int64_t nnz) { return nnz > kCsrSegment ? 2 * (nnz / kCsrSegment) : 0; }
 
@@ -1817,6 +1838,56 @@ int clane_csr_row_sums_f32(const int64_t *rowptr, const float *val, int64_t n_ro
                            const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, double *ws,
                            int64_t ws_len, double *sums, void *stream) {
     return csr_row_sums(rowptr, val, n_rows, nnz, long_rows, seg_ptr, item_long, n_long, n_items, ws, ws_len, sums, stream);
+}
+
+int clane_tsne_sqdist_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          const float *mu, float *sq, float *D, void *stream) {
+    return tsne_sqdist<float>(Z, table_rows, d, ldz, rows, n, mu, sq, D, stream);
+}
+int clane_tsne_sqdist_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                           const float *mu, float *sq, float *D, void *stream) {
+    return tsne_sqdist<bf16_t>(reinterpret_cast<const bf16_t *>(Z), table_rows, d, ldz, rows, n, mu, sq, D, stream);
+}
+int clane_tsne_affinities_f32(float *D, int64_t n, float perplexity, float *beta, void *stream) {
+    REQUIRE(n >= 2 && n <= kTsneMaxPoints, "tsne_affinities: n must be in [2, %d], got %lld", kTsneMaxPoints, (long long)n);
+    REQUIRE(perplexity > 0.f && perplexity < float(n), "tsne_affinities: perplexity %g is not in (0, n = %lld)",
+            double(perplexity), (long long)n);
+    REQUIRE(D && beta, "tsne_affinities: null pointer");
+    tsne_affinities_kernel<<<unsigned(n), kBlock, 0, (hipStream_t)stream>>>(D, n, perplexity, beta);
+    return check_launch("tsne_affinities");
+}
+int64_t clane_tsne_symmetrize_ws_len(int64_t n) { return tsne_sym_tiles(n) * (tsne_sym_tiles(n) + 1) / 2; }
+int clane_tsne_symmetrize_f32(float *P, int64_t n, double *partials, void *stream) {
+    REQUIRE(n >= 1 && n <= kTsneMaxPoints, "tsne_symmetrize: n must be in [1, %d], got %lld", kTsneMaxPoints, (long long)n);
+    REQUIRE(P && partials, "tsne_symmetrize: null pointer");
+    const int64_t nt = tsne_sym_tiles(n);
+    tsne_symmetrize_kernel<<<unsigned(nt * (nt + 1) / 2), kBlock, 0, (hipStream_t)stream>>>(P, n, int(nt), partials);
+    return check_launch("tsne_symmetrize");
+}
+int clane_tsne_forces_f32(const float *P, const float *Y, int64_t n, int32_t flags, float *F, void *stream) {
+    static_assert(kTsneForcesKL == CLANE_TSNE_FORCES_KL && kTsneForcesCached == CLANE_TSNE_FORCES_CACHED,
+                  "header and kernel disagree");
+    REQUIRE(n >= 1 && n <= kTsneMaxPoints, "tsne_forces: n must be in [1, %d], got %lld", kTsneMaxPoints, (long long)n);
+    REQUIRE((flags & ~(CLANE_TSNE_FORCES_KL | CLANE_TSNE_FORCES_CACHED)) == 0, "tsne_forces: unknown flags %d", flags);
+    REQUIRE(P && Y && F, "tsne_forces: null pointer");
+    REQUIRE((const void *)Y != (const void *)F, "tsne_forces: Y must not be the array being written");
+    const unsigned grid = unsigned(ceil_div(n, int64_t(kTsneRowsPerBlock)));
+    const int want_l = flags & CLANE_TSNE_FORCES_KL;
+    const bool vec = aligned16(P) && n % 4 == 0, nt = !(flags & CLANE_TSNE_FORCES_CACHED);
+    if (vec && nt) tsne_forces_kernel<true, true><<<grid, kBlock, 0, (hipStream_t)stream>>>(P, Y, n, want_l, F);
+    else if (vec) tsne_forces_kernel<true, false><<<grid, kBlock, 0, (hipStream_t)stream>>>(P, Y, n, want_l, F);
+    else if (nt) tsne_forces_kernel<false, true><<<grid, kBlock, 0, (hipStream_t)stream>>>(P, Y, n, want_l, F);
+    else tsne_forces_kernel<false, false><<<grid, kBlock, 0, (hipStream_t)stream>>>(P, Y, n, want_l, F);
+    return check_launch("tsne_forces");
+}
+int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha, double momentum, double lr, double plogp,
+                        float *V, float *G, float *Y_next, double *stats, void *stream) {
+    REQUIRE(n >= 1 && n <= kTsneMaxPoints, "tsne_step: n must be in [1, %d], got %lld", kTsneMaxPoints, (long long)n);
+    REQUIRE(F && Y && V && G && Y_next && stats, "tsne_step: null pointer");
+    REQUIRE(Y != Y_next, "tsne_step: Y must not be the array being written");
+    tsne_step_kernel<<<1, kTsneStepBlock, 0, (hipStream_t)stream>>>(F, Y, n, alpha, momentum, lr, plogp, V, G, Y_next,
+                                                                    stats);
+    return check_launch("tsne_step");
 }
 
 }  // extern "C"

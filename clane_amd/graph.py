@@ -688,6 +688,53 @@ class Graph(torch.utils.data.Dataset):
         pca = ContentPCA(dim, whiten=whiten).fit_table(eng, table, vertices)
         return pca.transform_table(eng, table, vertices).cpu(), pca
 
+    def layout(self, table: str = "Z", vertices=None, max_points: int = 20000, seed: int = 0, labels=None,
+               **tsne_kwargs):
+        """``(Y [n, 2] on the host, the laid-out vertex indices, info)``: the exact t-SNE layout (extension, layout.py:
+        distances, perplexity search and every iteration on the GPU) of the CURRENT embeddings (``table="X"``: of the
+        content) of ``vertices`` (default: all).  More than ``max_points`` of them: the first ``max_points`` of a torch
+        permutation seeded with ``seed``, sorted; ``Y`` is in the order of the returned indices.  ``labels`` -- a file of
+        ``id<TAB>class`` lines, one class per vertex of the graph, or ``(vertices, classes)`` -- adds ``"classes"`` (per
+        laid-out vertex, None where unlabelled) and ``"neighbour_agreement"`` (k = 5, over the labelled ones) to
+        ``info``, next to ``n, sampled, table, perplexity, iterations, kl, kl_init, grad_norm, kl_trace``.
+        ``tsne_kwargs`` go to ``layout.TSNE``.  Reads the engine's table where it lies and changes no state.  One GPU only."""
+        from .classify import read_labels
+        from .layout import MIN_POINTS, TSNE, neighbour_agreement, sample_vertices
+        if isinstance(max_points, bool) or int(max_points) != max_points or int(max_points) < MIN_POINTS:
+            raise ValueError(f"layout: max_points must be an integer >= {MIN_POINTS}, got {max_points!r}")
+        cls_of = None
+        if labels is not None:
+            if isinstance(labels, (str, Path)):
+                lv, ly, names = read_labels(Path(labels), self.vertex_ids)
+                lc = [names[c] for c in ly]
+            elif isinstance(labels, tuple) and len(labels) == 2:
+                lv, lc = list(labels[0]), list(labels[1])
+            else:
+                lc = list(labels)
+                lv = list(range(len(self)))
+            if len(lv) != len(lc):
+                raise ValueError("layout: one class per labelled vertex")
+            cls_of = {int(v): (c.item() if isinstance(c, torch.Tensor) else c) for v, c in zip(lv, lc)}
+        pool = torch.arange(len(self)) if vertices is None else torch.as_tensor(vertices, dtype=torch.int64).reshape(-1)
+        pick, sampled = sample_vertices(int(pool.numel()), int(max_points), seed)
+        chosen = pool[pick]
+        tsne = TSNE(self.engine(), **tsne_kwargs)
+        tsne.check_points(int(chosen.numel()))                  # before the table is touched
+        tab, rows = tsne.table_and_rows(chosen, table)
+        fit = tsne.fit(tab, rows, seed=seed)
+        Y = fit.Y.cpu()
+        info = {"n": int(chosen.numel()), "sampled": bool(sampled), "table": table, "perplexity": tsne.perplexity,
+                "iterations": fit.iterations, "kl": fit.kl, "kl_init": fit.kl_init, "grad_norm": fit.grad_norm,
+                "kl_trace": list(fit.kl_trace)}
+        if cls_of is not None:
+            classes = [cls_of.get(int(v)) for v in chosen.tolist()]
+            known = [i for i, c in enumerate(classes) if c is not None]
+            index = {c: i for i, c in enumerate(sorted({classes[i] for i in known}, key=str))}
+            info["classes"] = classes
+            info["neighbour_agreement"] = (neighbour_agreement(Y[known], [index[classes[i]] for i in known], k=5)
+                                           if len(known) > 5 else None)
+        return Y, chosen, info
+
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on
         every call: a caller that changes Phi between rounds gets the new P)."""

@@ -73,7 +73,11 @@ extern "C" {
                              *    value sums -- the products of a randomized PCA on a bag of words)
                              *    + clane_spmm_update_tiles_f32, clane_spmm_update_class_tiles_f32,
                              *    clane_spmm_update_owned_tiles_f32 (every column tile of a K3 pass in ONE launch, bit for
-                             *    bit the per-tile calls) and the flag CLANE_OWNED_EPILOGUE_AHEAD of the owned calls */
+                             *    bit the per-tile calls) and the flag CLANE_OWNED_EPILOGUE_AHEAD of the owned calls
+                             *    + clane_tsne_sqdist_*, clane_tsne_affinities_f32, clane_tsne_symmetrize_f32,
+                             *    clane_tsne_symmetrize_ws_len, clane_tsne_forces_f32, clane_tsne_step_f32 (2-D layout: exact
+                             *    t-SNE of rows of the table -- all-pairs distances on the matrix cores, the perplexity
+                             *    search, the joint probabilities and the two kernels of an iteration) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -877,6 +881,48 @@ int clane_csr_spmm_f32(const int64_t *rowptr, const int32_t *col, const float *v
 int clane_csr_row_sums_f32(const int64_t *rowptr, const float *val, int64_t n_rows, int64_t nnz, const int32_t *long_rows,
                            const int64_t *seg_ptr, const int32_t *item_long, int64_t n_long, int64_t n_items, double *ws,
                            int64_t ws_len, double *sums, void *stream);
+
+/* ---- 2-D layout: exact t-SNE (csrc/tsne.h) ------------------------------------------------------------------------------
+ * The formulas are scikit-learn's TSNE(method="exact"); n points, 2 <= n <= CLANE_TSNE_MAX_POINTS; D / P [n, n] fp32
+ * contiguous; Y, V, G [n, 2] fp32 contiguous.  A fit calls them in this order.  No allocation, no synchronisation, no
+ * atomics; the order of every sum is a function of n alone: two calls give the same bits.
+ *
+ * tsne_sqdist: D[i, j] = max(0, |a_i|^2 + |a_j|^2 - 2 a_i . a_j), a_i = Z[rows[i], 0:d) - mu formed by one fp32
+ *   subtraction (a `rows` entry outside [0, table_rows) is the row z = 0); mu [d] fp32, the caller's column mean of the
+ *   listed rows (clane_column_sums_*).  |a|^2 is one fmaf per k in k order (sq [n] fp32: workspace, left filled); the
+ *   dots run in the order of the library's one tile contraction (mfma_slice).  Only the 128 x 128 tile pairs ti <= tj are
+ *   computed and each value is written to D[i, j] and D[j, i]: D is bitwise symmetric, its diagonal exactly 0.
+ * tsne_affinities: in place, row i of D becomes p_{j|i} = exp(-beta_i (D_ij - min_j D_ij)) / sum, 0 on the diagonal;
+ *   beta_i by scikit-learn's _binary_search_perplexity in fp32: from 1, doubled / halved until bracketed, then bisected,
+ *   at most 100 steps, until |H_i - ln(perplexity)| <= 1e-5; beta [n] = the beta_i the row was written with.  One
+ *   workgroup per row: thread t of 256 adds j = t, t + 256, .. in order (fp32), the threads are added in double.
+ * tsne_symmetrize: in place, P_ij = max((p_{j|i} + p_{i|j}) / 2n, 2.220446e-16), 0 on the diagonal; bitwise symmetric.
+ *   partials [clane_tsne_symmetrize_ws_len(n)] doubles: sum p ln p of each pair of 64 x 64 tiles, pairs in the order
+ *   (0, 0), (0, 1), .., (1, 1), ..; their sum in that order is the constant of the KL below.
+ * tsne_forces: F [n, 6] fp32 = per row i, with q_ij = 1 / (1 + |y_i - y_j|^2):
+ *   F[i, 0:2] = sum_j P_ij q_ij (y_i - y_j), F[i, 2:4] = sum_j q_ij^2 (y_i - y_j), F[i, 4] = sum_{j != i} q_ij and, with
+ *   CLANE_TSNE_FORCES_KL, F[i, 5] = sum_j P_ij log1p(|y_i - y_j|^2) (0 without).  P is read once, Y through LDS; lane l of
+ *   64 adds the columns 2048 c + 256 m + 4 l + u in (c, m, u) order, the lanes are folded by the xor butterfly.
+ *   CLANE_TSNE_FORCES_CACHED: plain loads of P instead of non-temporal ones -- the same bits.
+ * tsne_step: S = sum_i F[i, 4] (double; thread t of 1024 adds i = t, t + 1024, .., the threads in order),
+ *   g_i = 4 (alpha F[i, 0:2] - F[i, 2:4] / S); scikit-learn's _gradient_descent per coordinate in double, stored fp32:
+ *   gain += 0.2 where v g < 0, else gain *= 0.8, floor 0.01; v = momentum v - lr gain g; Y_next = Y + v.  V and G are
+ *   updated in place; Y_next must not be Y.  stats [4] doubles: KL = plogp + sum_i F[i, 5] + ln S (plogp: the sum of
+ *   tsne_symmetrize's partials; valid at alpha = 1 and when the forces were taken with CLANE_TSNE_FORCES_KL), |g|, S,
+ *   sum_i F[i, 5]. */
+#define CLANE_TSNE_MAX_POINTS 65536
+#define CLANE_TSNE_FORCES_KL 1
+#define CLANE_TSNE_FORCES_CACHED 2
+int clane_tsne_sqdist_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          const float *mu, float *sq, float *D, void *stream);
+int clane_tsne_sqdist_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                           const float *mu, float *sq, float *D, void *stream);
+int clane_tsne_affinities_f32(float *D, int64_t n, float perplexity, float *beta, void *stream);
+int64_t clane_tsne_symmetrize_ws_len(int64_t n);
+int clane_tsne_symmetrize_f32(float *P, int64_t n, double *partials, void *stream);
+int clane_tsne_forces_f32(const float *P, const float *Y, int64_t n, int32_t flags, float *F, void *stream);
+int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha, double momentum, double lr, double plogp,
+                        float *V, float *G, float *Y_next, double *stats, void *stream);
 
 #ifdef __cplusplus
 }
