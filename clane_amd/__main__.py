@@ -83,6 +83,9 @@ def embedding(args):
         if not isinstance(node_clu, dict) or ("labels" not in node_clu and "clusters" not in node_clu):
             raise ValueError("node_clustering: the section needs 'labels', the file of id<TAB>class lines, or 'clusters', "
                              "the number of clusters")
+        # scoring without labels: silhouette: true, silhouette_metric, silhouette_points; clusters may be a list (cluster.py)
+        from . import cluster as cluster_mod
+        node_clu_scoring = cluster_mod.check_section(node_clu)
     # optional section (extension): content_reduction: {dim: 128, center: true, whiten: false, load: pca.npz} -- the
     # content's principal components instead of the content (reduce.py); checked before the graph loads.  With
     # sparse: C.npz (and oversample / power_iterations / seed) the content is a CSR bag of words, read and validated here
@@ -296,7 +299,7 @@ def embedding(args):
             if not labels_file.is_absolute():
                 labels_file = Path(args.data_root) / labels_file
         kw = {key: node_clu[key] for key in ("restarts", "seed", "max_iter") if key in node_clu}
-        kw.update(k=node_clu.get("clusters"), labels=labels_file, return_assignments=True)
+        kw.update(k=node_clu.get("clusters"), labels=labels_file, return_assignments=True, **node_clu_scoring)
         tables = {"Z": g.cluster(table="Z", **kw)}
         if node_clu.get("baseline", False):
             tables["X"] = g.cluster(table="X", **kw)

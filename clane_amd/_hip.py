@@ -154,6 +154,11 @@ SIGNATURES["clane_tsne_symmetrize_f32"] = (C.c_int, [_p, _i64, _p, _p])
 SIGNATURES["clane_tsne_forces_f32"] = (C.c_int, [_p, _p, _i64, _i32, _p, _p])
 SIGNATURES["clane_tsne_step_f32"] = (
     C.c_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p])
+SILHOUETTE_METRICS = {"euclidean": 0, "cosine": 1}      # CLANE_SILHOUETTE_*; silhouette (csrc/silhouette.h)
+for _s in ("f32", "f64", "bf16"):
+    SIGNATURES[f"clane_silhouette_norms_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p])
+    SIGNATURES[f"clane_silhouette_sums_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _i32, _i64, _i64, _p, _p])
 
 
 def probe_padded_classes(C_: int) -> int:
@@ -640,6 +645,18 @@ class KernelBackend(abc.ABC):
     def tsne_step(self, F, Y, alpha: float, momentum: float, lr: float, plogp: float, V, G, Y_next, stats):
         """scikit-learn's gradient-descent update from the force sums; stats (float64 [4]) = KL, |g|, S, sum l."""
         raise NotImplementedError(f"{type(self).__name__} has no tsne_step")
+
+    # silhouette (cluster.py): optional in the same way -- Silhouette is the only caller.  order: TABLE ROWS (int32) grouped
+    # by cluster, seg int64 [K + 1] the clusters' starts in it; mu and nrm in the accumulate dtype.
+    def silhouette_norms(self, Z, d: int, order, mu, metric: str, nrm):
+        """nrm[p] of a_p = Z[order[p], :d] - mu: |a_p|^2 ("euclidean") or 1 / |a_p|, 0 for a zero row ("cosine"), the
+        squared norm taken through the very contraction the dots of silhouette_sums run through."""
+        raise NotImplementedError(f"{type(self).__name__} has no silhouette_norms")
+
+    def silhouette_sums(self, Z, d: int, order, seg, mu, nrm, metric: str, p0: int, p1: int, S):
+        """S[p - p0, c] (float64, [>= p1 - p0, K]) = the sum over the positions j of cluster c of dist(p, j), p in
+        [p0, p1); the term j == p is exactly 0, an empty cluster's column zeros; the same bits for every [p0, p1)."""
+        raise NotImplementedError(f"{type(self).__name__} has no silhouette_sums")
 
     # owned class rows (csrc/spmm_update.h, spmm_owned_kernel): optional in the same way -- a backend without them keeps
     # every class row on spmm_update_class, and SweepEngine asks `has_spmm_owned` before it plans for them
@@ -1517,6 +1534,36 @@ class HipKernels(KernelBackend):
                      _vec(F, f32, "F"), _vec(Y, f32, "Y"), n, float(alpha), float(momentum), float(lr), float(plogp),
                      _vec(V, f32, "V"), _vec(G, f32, "G"), _vec(Y_next, f32, "Y_next"), _vec(stats, torch.float64, "stats"),
                      self._stream(Y))
+
+    # -- silhouette -------------------------------------------------------------------------
+    def _silhouette_args(self, what: str, Z, d: int, order, mu, metric: str, nrm):
+        if metric not in SILHOUETTE_METRICS:
+            raise ValueError(f"{what}: metric must be one of {sorted(SILHOUETTE_METRICS)}, got {metric!r}")
+        acc = acc_dtype(Z.dtype)
+        n = order.numel()
+        if mu.numel() != d or nrm.numel() != n:
+            raise ValueError(f"{what}: mu needs d = {d} entries and nrm one per position ({n})")
+        zp, ldz = _mat(Z, "Z")
+        return (zp, Z.shape[0], d, ldz, _vec(order, torch.int32, "order"), n), _vec(mu, acc, "mu"), _vec(nrm, acc, "nrm")
+
+    def silhouette_norms(self, Z, d: int, order, mu, metric: str, nrm):
+        head, mup, np_ = self._silhouette_args("silhouette_norms", Z, d, order, mu, metric, nrm)
+        self._invoke(self._fn("clane_silhouette_norms", Z.dtype), "clane_silhouette_norms",
+                     *head, mup, SILHOUETTE_METRICS[metric], np_, self._stream(Z))
+
+    def silhouette_sums(self, Z, d: int, order, seg, mu, nrm, metric: str, p0: int, p1: int, S):
+        head, mup, np_ = self._silhouette_args("silhouette_sums", Z, d, order, mu, metric, nrm)
+        n, K = order.numel(), seg.numel() - 1
+        p0, p1 = int(p0), int(p1)
+        if K < 1 or not 0 <= p0 <= p1 <= n:
+            raise ValueError(f"silhouette_sums: seg needs K + 1 >= 2 offsets and 0 <= p0 <= p1 <= n = {n}, got K = {K}, "
+                             f"[{p0}, {p1})")
+        if S.dtype != torch.float64 or S.dim() != 2 or S.shape[1] != K or S.shape[0] < p1 - p0 or not S.is_contiguous():
+            raise ValueError(f"silhouette_sums: S must be contiguous float64 [>= {p1 - p0}, {K}], got {tuple(S.shape)} "
+                             f"{S.dtype}")
+        self._invoke(self._fn("clane_silhouette_sums", Z.dtype), "clane_silhouette_sums",
+                     *head, _vec(seg, torch.int64, "seg"), K, mup, np_, SILHOUETTE_METRICS[metric], p0, p1, S.data_ptr(),
+                     self._stream(Z))
 
     # -- CosineSimilarity on explicit pairs ------------------------------------------------
     def pair_cosine(self, A, B, d: int, out, ws):

@@ -12,11 +12,16 @@ arbitrary rows of the table.
 
 The initial centres are k-means++ from a seeded torch generator per restart, NOT scikit-learn's random stream: inertia,
 NMI and ARI are defined as scikit-learn defines them, the partitions found are those of this module's seeds.
+
+Without labels a clustering is scored by its silhouette (``Silhouette``: the n x K sums of distances of
+csrc/silhouette.h on the matrix cores, the n x n distances never exist), Calinski-Harabasz and Davies-Bouldin, and
+``select_clusters`` keeps the number of clusters with the highest mean silhouette -- inertia falls as k grows and can
+do neither.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -256,3 +261,314 @@ class KMeans:
                                         "iterations": fit.iterations.tolist()}})
         self.last_fit = fit
         return out
+
+
+# ---- scores without labels ----------------------------------------------------------------------------------------
+# The silhouette of a partition, from the n x K sums of distances of csrc/silhouette.h (the n x n distances never exist),
+# and the two centre-based indices.  All three as scikit-learn defines them (silhouette_samples, calinski_harabasz_score,
+# davies_bouldin_score), in float64; cluster ids that own no row are left out of all of them.
+SILHOUETTE_METRICS = ("euclidean", "cosine")
+SILHOUETTE_SUMS_BYTES = 1 << 27     # the default block of positions keeps the sums S [block, K] within this
+
+
+def dense_partition(part) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ids, inverse) of any integer partition: the sorted distinct values and each row's index among them."""
+    part = torch.as_tensor(part)
+    if part.dtype.is_floating_point or part.dtype == torch.bool or part.dim() != 1:
+        raise ValueError(f"a partition is one integer per row, got {part.dtype} {tuple(part.shape)}")
+    ids, inv = torch.unique(part.long(), sorted=True, return_inverse=True)
+    return ids, inv
+
+
+def silhouette_finish(S: torch.Tensor, own: torch.Tensor, sizes: torch.Tensor) -> torch.Tensor:
+    """Per-row silhouette (float64) from S [m, K] (float64: S[i, c] = the sum of row i's distances to the members of
+    cluster c, its own term 0), the rows' clusters ``own`` [m] and the cluster sizes [K]: a = S[i, own] / (n_own - 1),
+    b = the minimum over the OTHER NON-EMPTY clusters of S[i, c] / n_c, s = (b - a) / max(a, b); s = 0 for a row alone in
+    its cluster and where max(a, b) = 0."""
+    cnt = sizes.to(S.device).double()
+    own = own.to(S.device).long()
+    n_own = cnt[own]
+    a = S.gather(1, own[:, None])[:, 0] / (n_own - 1.0).clamp(min=1.0)
+    means = torch.where(cnt[None, :] > 0, S / cnt.clamp(min=1.0)[None, :], torch.full_like(S, float("inf")))
+    b = means.scatter(1, own[:, None], float("inf")).min(1).values
+    m = torch.maximum(a, b)
+    ok = (n_own > 1) & (m > 0)
+    return torch.where(ok, (b - a) / torch.where(ok, m, torch.ones_like(m)), torch.zeros_like(m))
+
+
+def silhouette_reference(X, part, metric: str = "euclidean") -> torch.Tensor:
+    """The definition, restated in float64 on the host: the per-row silhouette of the rows of ``X`` [n, d] under the
+    integer partition ``part`` [n], with every pairwise distance formed -- ``euclidean``: sqrt(sum_k (x_ik - x_jk)^2);
+    ``cosine``: max(0, 1 - x_i . x_j / (|x_i| |x_j|)), a zero row at distance 1 from every other row.  O(n^2 d): for tests."""
+    if metric not in SILHOUETTE_METRICS:
+        raise ValueError(f"silhouette_reference: metric must be one of {SILHOUETTE_METRICS}, got {metric!r}")
+    X = torch.as_tensor(X).detach().cpu().double()
+    ids, own = dense_partition(torch.as_tensor(part).cpu())
+    n, K = int(X.shape[0]), int(ids.numel())
+    if own.numel() != n:
+        raise ValueError("silhouette_reference: one cluster per row")
+    if K < 2:
+        raise ValueError("silhouette_reference: the silhouette needs at least two non-empty clusters")
+    if metric == "cosine":
+        nr = (X * X).sum(1).sqrt()
+        r = torch.where(nr > 0, 1.0 / nr.clamp(min=1e-300), torch.zeros_like(nr))
+    member = torch.nn.functional.one_hot(own, K).double()
+    S = torch.empty(n, K, dtype=torch.float64)
+    for a in range(0, n, 256):
+        x = X[a:a + 256]
+        if metric == "euclidean":
+            D = ((x[:, None, :] - X[None, :, :]) ** 2).sum(-1).sqrt()
+        else:
+            D = (1.0 - (x @ X.T) * r[a:a + 256, None] * r[None, :]).clamp(min=0.0)
+        i = torch.arange(x.shape[0])
+        D[i, a + i] = 0.0
+        S[a:a + 256] = D @ member
+    return silhouette_finish(S, own, member.sum(0).long())
+
+
+def calinski_harabasz(centres: torch.Tensor, sizes: torch.Tensor, sq_dist: torch.Tensor) -> float:
+    """scikit-learn's calinski_harabasz_score in float64 from the clusters' means ``centres`` [K, d], their sizes [K]
+    and the rows' SQUARED distances to their own cluster's mean [n]: (between / (k - 1)) / (within / (n - k)) over the k
+    non-empty clusters, 1.0 where within = 0."""
+    w = sizes.double()
+    live = w > 0
+    c, w = centres.double()[live.to(centres.device)].to(w.device), w[live]
+    k, n = int(w.numel()), float(w.sum())
+    if k < 2 or n <= k:
+        raise ValueError(f"calinski_harabasz: needs 2 <= non-empty clusters < rows, got {k} clusters of {int(n)} rows")
+    mean = (w[:, None] * c).sum(0) / n
+    between = float((w * ((c - mean) ** 2).sum(1)).sum())
+    within = float(sq_dist.double().sum())
+    return 1.0 if within == 0.0 else between * (n - k) / (within * (k - 1.0))
+
+
+def davies_bouldin(centres: torch.Tensor, sizes: torch.Tensor, dist: torch.Tensor, assign: torch.Tensor) -> float:
+    """scikit-learn's davies_bouldin_score in float64 from the clusters' means ``centres`` [K, d], their sizes [K], the
+    rows' distances (NOT squared) to their own cluster's mean [n] and the rows' clusters [n]: the mean over the non-empty
+    clusters of max_{c' != c} (s_c + s_c') / |mu_c - mu_c'|, s_c the mean distance of c's rows to its mean; coincident
+    means do not count, and the score is 0 where every s_c or every distance between means is 0."""
+    w = sizes.to(dist.device).double()
+    live = torch.nonzero(w > 0)[:, 0]
+    if live.numel() < 2:
+        raise ValueError(f"davies_bouldin: needs at least two non-empty clusters, got {int(live.numel())}")
+    c = centres.to(dist.device).double()[live]
+    dist, assign = dist.double(), assign.to(dist.device).long()
+    zero = torch.zeros((), dtype=torch.float64, device=dist.device)
+    intra = torch.stack([torch.where(assign == j, dist, zero).sum() for j in live.tolist()]) / w[live]
+    cd = ((c[:, None, :] - c[None, :, :]) ** 2).sum(-1).sqrt()
+    if bool((intra.abs() <= 1e-8).all()) or bool((cd.abs() <= 1e-8).all()):      # numpy's allclose(x, 0)
+        return 0.0
+    cd = torch.where(cd == 0, torch.full_like(cd, float("inf")), cd)
+    return float(((intra[:, None] + intra[None, :]) / cd).max(1).values.mean())
+
+
+@dataclass
+class SilhouetteResult:
+    samples: torch.Tensor               # [n] float64, in the order of ``rows``, on the device
+    sizes: torch.Tensor                 # [K] int64
+    per_cluster: torch.Tensor           # [K] float64: the mean of a cluster's rows, NaN for an empty cluster
+    mean: float
+    sums: Optional[torch.Tensor] = None  # [n, K] float64 in the order of ``rows``, with ``keep_sums``
+
+
+class Silhouette:
+    """The exact silhouette of a partition of rows of a table of ``engine``: one norms call and, per block of
+    ``block_rows`` positions (default: what keeps the sums within 128 MiB; rounded up to the kernel's 128-row tile), one
+    sums call of csrc/silhouette.h and the finish in float64 torch on the device.  The result does not depend on the block
+    size, bit for bit."""
+
+    def __init__(self, engine, metric: str = "euclidean", block_rows: Optional[int] = None):
+        try:
+            require_one_gpu(engine)
+        except NotImplementedError:
+            raise NotImplementedError(
+                f"the silhouette runs on ONE GPU only: it reads arbitrary rows of the table, which this engine divides "
+                f"over {engine.world} ranks (exchange={engine.exchange!r}); several GPUs are out of scope") from None
+        if metric not in SILHOUETTE_METRICS:
+            raise ValueError(f"Silhouette: metric must be one of {SILHOUETTE_METRICS}, got {metric!r}")
+        if block_rows is not None and (isinstance(block_rows, bool) or int(block_rows) != block_rows or int(block_rows) < 1):
+            raise ValueError(f"Silhouette: block_rows must be a positive integer, got {block_rows!r}")
+        self.eng, self.k, self.metric = engine, engine.k, metric
+        self.block_rows = None if block_rows is None else int(block_rows)
+        self.passes = {"norms": 0, "sums": 0}       # kernel calls of the last samples()
+
+    def table_and_rows(self, vertices, table: str = "Z"):
+        """(table, int32 rows) for vertex indices: the current embeddings ("Z") or the content embeddings ("X")."""
+        return table_and_rows(self.eng, vertices, table)
+
+    def column_mean(self, Z, rows) -> torch.Tensor:
+        """The column mean of the listed rows (float64 [d]) through the library's deterministic column sums."""
+        d, n = self.eng.d, int(rows.numel())
+        ws = torch.empty(max(1, self.k.column_sums_ws_len(n, d)), dtype=torch.float64, device=Z.device)
+        sums = torch.empty(d, dtype=torch.float64, device=Z.device)
+        self.k.column_sums(Z, d, rows, ws, sums)
+        return sums / n
+
+    def samples(self, Z: torch.Tensor, rows: torch.Tensor, part: torch.Tensor, k: Optional[int] = None,
+                mu: Optional[torch.Tensor] = None, keep_sums: bool = False) -> SilhouetteResult:
+        """Score the rows ``rows`` (int32 table rows of ``Z``) under the partition ``part`` (one cluster in [0, k) per
+        row; ``k`` defaults to the largest + 1; ids without rows are empty clusters and are left out).  ``mu``: the shift
+        subtracted from every row for ``euclidean`` (default: the rows' column mean -- distances do not depend on it, the
+        rounding of the Gram trick does); ``cosine`` takes the rows as they are."""
+        dev, d, kern = Z.device, self.eng.d, self.k
+        acc = _hip.acc_dtype(Z.dtype)
+        rows = rows.to(dev, torch.int32).contiguous()
+        part = torch.as_tensor(part)
+        if part.dtype.is_floating_point or part.dtype == torch.bool:
+            raise ValueError(f"samples: the partition must be integers, got {part.dtype}")
+        part = part.to(dev, torch.int64).reshape(-1)
+        n = int(rows.numel())
+        if part.numel() != n:
+            raise ValueError(f"samples: one cluster per row, got {part.numel()} for {n} rows")
+        if n < 2:
+            raise ValueError("samples: the silhouette needs at least two rows")
+        lo, hi = int(part.min()), int(part.max())
+        K = int(k) if k is not None else hi + 1
+        if lo < 0 or hi >= K:
+            raise ValueError(f"samples: clusters must be in [0, {K}), got [{lo}, {hi}]")
+        sizes = torch.bincount(part, minlength=K)
+        if int((sizes > 0).sum()) < 2:
+            raise ValueError("samples: the silhouette needs at least two non-empty clusters")
+        perm = torch.sort(part, stable=True).indices
+        order, own = rows[perm].contiguous(), part[perm]
+        seg = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), sizes.cumsum(0)])
+        if self.metric == "cosine":
+            if mu is not None:
+                raise ValueError("samples: mu belongs to the euclidean metric; a shift changes cosine distances")
+            shift = torch.zeros(d, dtype=acc, device=dev)
+        else:
+            shift = (self.column_mean(Z, rows) if mu is None else torch.as_tensor(mu).reshape(-1)).to(dev, acc).contiguous()
+            if shift.numel() != d:
+                raise ValueError(f"samples: mu needs d = {d} entries")
+        self.passes = {"norms": 0, "sums": 0}
+        nrm = torch.empty(n, dtype=acc, device=dev)
+        kern.silhouette_norms(Z, d, order, shift, self.metric, nrm)
+        self.passes["norms"] += 1
+        block = self.block_rows if self.block_rows is not None else max(1, SILHOUETTE_SUMS_BYTES // (8 * K))
+        block = min(-(-block // 128) * 128, -(-n // 128) * 128)
+        S = torch.empty(min(block, n), K, dtype=torch.float64, device=dev)
+        s_sorted = torch.empty(n, dtype=torch.float64, device=dev)
+        kept = torch.empty(n, K, dtype=torch.float64, device=dev) if keep_sums else None
+        for p0 in range(0, n, block):
+            p1 = min(n, p0 + block)
+            kern.silhouette_sums(Z, d, order, seg, shift, nrm, self.metric, p0, p1, S)
+            self.passes["sums"] += 1
+            s_sorted[p0:p1] = silhouette_finish(S[:p1 - p0], own[p0:p1], sizes)
+            if kept is not None:
+                kept[perm[p0:p1]] = S[:p1 - p0]
+        s = torch.empty_like(s_sorted)
+        s[perm] = s_sorted
+        bounds = seg.tolist()
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        per = torch.stack([s_sorted[bounds[c]:bounds[c + 1]].sum() / (bounds[c + 1] - bounds[c])
+                           if bounds[c + 1] > bounds[c] else nan for c in range(K)])    # cluster by cluster: a fixed order
+        return SilhouetteResult(samples=s, sizes=sizes, per_cluster=per, mean=float(s_sorted.sum() / n), sums=kept)
+
+
+# ---- choosing k ---------------------------------------------------------------------------------------------------
+SELECTION_FIELDS = ("clusters", "inertia", "silhouette", "calinski_harabasz", "davies_bouldin", "empty")
+
+
+def check_cluster_counts(k, what: str = "cluster") -> Tuple[List[int], bool]:
+    """(the list of cluster counts, whether ``k`` was a sequence): one integer >= 1, or a non-empty sequence of distinct
+    integers >= 2 (every candidate is scored by its silhouette, which needs two clusters)."""
+    def integer(v):
+        return not isinstance(v, bool) and isinstance(v, int)
+    if isinstance(k, torch.Tensor):
+        k = k.tolist()
+    if isinstance(k, (list, tuple, range)):
+        ks = list(k)
+        if not ks or not all(integer(v) and v >= 2 for v in ks) or len(set(ks)) != len(ks):
+            raise ValueError(f"{what}: a list of cluster counts needs distinct integers >= 2, got {k!r}")
+        return ks, True
+    if not integer(k) or k < 1:
+        raise ValueError(f"{what}: the number of clusters must be an integer >= 1 or a list of them, got {k!r}")
+    return [k], False
+
+
+def select_clusters(ks: Sequence[int], run: Callable[[int], dict]) -> dict:
+    """Fit and score every candidate (``run(k)``: the result of one scored clustering, with ``silhouette`` -- None where
+    the fit left fewer than two non-empty clusters) and return the result of the one with the highest mean silhouette,
+    ties to the smaller ``k``, with ``selection = {criterion, candidates, chosen}`` added."""
+    results = [run(int(k)) for k in ks]
+    best = None
+    for i, r in enumerate(results):
+        if r.get("silhouette") is None:
+            continue
+        if best is None or r["silhouette"] > results[best]["silhouette"] or \
+                (r["silhouette"] == results[best]["silhouette"] and r["clusters"] < results[best]["clusters"]):
+            best = i
+    if best is None:
+        raise ValueError("cluster: no candidate left two non-empty clusters to score")
+    out = dict(results[best])
+    out["selection"] = {"criterion": "silhouette",
+                        "candidates": [{f: r.get(f) for f in SELECTION_FIELDS} for r in results],
+                        "chosen": int(results[best]["clusters"])}
+    return out
+
+
+def score_fit(km: KMeans, sil: Silhouette, Z: torch.Tensor, rows: torch.Tensor, fit: KMeansFit,
+              pick: Optional[torch.Tensor] = None) -> dict:
+    """``silhouette`` (mean, over the positions ``pick`` of ``rows`` when given), ``silhouette_per_cluster``,
+    ``calinski_harabasz`` and ``davies_bouldin`` (over all rows) of the best restart of ``fit``.  The two indices are
+    taken about the MEANS of the final assignment (one kmeans_update call), which are the fit's centres once it has
+    converged; the silhouette is None where fewer than two clusters own a row."""
+    dev, d, kern = Z.device, km.eng.d, km.k
+    acc = _hip.acc_dtype(Z.dtype)
+    rows = rows.to(dev, torch.int32).contiguous()
+    n, b = int(rows.numel()), fit.best_restart
+    assign = fit.assign[:, b].long()
+    K = int(fit.centres.shape[1])
+    sizes = torch.bincount(assign, minlength=K)
+    if int((sizes > 0).sum()) < 2:
+        return {"silhouette": None, "silhouette_per_cluster": None, "calinski_harabasz": None, "davies_bouldin": None}
+    perm = torch.sort(assign, stable=True).indices
+    seg = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), sizes.cumsum(0)])
+    old = fit.centres[b:b + 1].contiguous()
+    means, msq = torch.empty_like(old), torch.empty(1, K, dtype=acc, device=dev)
+    ws = torch.empty(kern.kmeans_update_ws_len(n, 1, K, d), dtype=acc, device=dev)
+    kern.kmeans_update(Z, d, rows[perm].contiguous(), seg, old, ws, means, msq)
+    means = means[0].double()
+    d2 = torch.empty(n, dtype=torch.float64, device=dev)
+    for a in range(0, n, 1 << 16):                              # O(n d) plumbing: the rows' distances to their own mean
+        diff = km._gathered(Z, rows[a:a + (1 << 16)], acc).double() - means[assign[a:a + (1 << 16)]]
+        d2[a:a + (1 << 16)] = (diff * diff).sum(1)
+    if pick is None:
+        res = sil.samples(Z, rows, assign, k=K)
+    else:
+        pick = pick.to(dev)
+        sub = assign[pick]
+        res = sil.samples(Z, rows[pick], sub, k=K) if int((torch.bincount(sub, minlength=K) > 0).sum()) >= 2 else None
+    per = None if res is None else [None if v != v else v for v in res.per_cluster.tolist()]
+    return {"silhouette": None if res is None else res.mean, "silhouette_per_cluster": per,
+            "calinski_harabasz": calinski_harabasz(means, sizes, d2) if n > int((sizes > 0).sum()) else None,
+            "davies_bouldin": davies_bouldin(means, sizes, d2.sqrt(), assign)}
+
+
+def check_section(section) -> dict:
+    """The ``node_clustering`` section's keys for scoring without labels, validated before any work: ``silhouette`` (true /
+    false), ``silhouette_metric`` (euclidean / cosine), ``silhouette_points`` (an integer >= 2 or null: score at most so
+    many sampled vertices) and ``clusters`` (an integer, or a list of them: the count of highest mean silhouette is kept;
+    a list implies ``silhouette``).  Returns the keyword arguments they add to ``Graph.cluster``."""
+    kw = {}
+    listed = False
+    if isinstance(section.get("clusters"), (list, tuple)):      # a single count is read as it always was
+        _, listed = check_cluster_counts(section["clusters"], "node_clustering: clusters")
+    if "silhouette" in section and not isinstance(section["silhouette"], bool):
+        raise ValueError(f"node_clustering: silhouette must be true or false, got {section['silhouette']!r}")
+    on = bool(section.get("silhouette", False)) or listed
+    if "silhouette_metric" in section and section["silhouette_metric"] not in SILHOUETTE_METRICS:
+        raise ValueError(f"node_clustering: silhouette_metric must be one of {list(SILHOUETTE_METRICS)}, got "
+                         f"{section['silhouette_metric']!r}")
+    if "silhouette_points" in section:
+        p = section["silhouette_points"]
+        if p is not None and (isinstance(p, bool) or not isinstance(p, int) or p < 2):
+            raise ValueError(f"node_clustering: silhouette_points must be an integer >= 2 or null, got {p!r}")
+    for key in ("silhouette_metric", "silhouette_points"):
+        if key in section and not on:
+            raise ValueError(f"node_clustering: {key} belongs to silhouette: true (or a list of clusters)")
+        if key in section:
+            kw[key] = section[key]
+    if on:
+        kw["silhouette"] = True
+    return kw

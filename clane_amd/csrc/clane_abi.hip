@@ -23,6 +23,7 @@
 #include "projection.h"
 #include "sparse_rows.h"
 #include "spmm_update.h"
+#include "silhouette.h"
 #include "tsne.h"
 
 namespace {
@@ -1254,6 +1255,48 @@ int tsne_sqdist(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const in
     return check_launch("tsne_sqdist");
 }
 
+// ---- silhouette (silhouette.h) ------------------------------------------------------------------------------------------
+inline int silhouette_check(const char *what, int64_t table_rows, int64_t n, int32_t d, int64_t ldz, int32_t metric) {
+    static_assert(kSilEuclidean == CLANE_SILHOUETTE_EUCLIDEAN && kSilCosine == CLANE_SILHOUETTE_COSINE,
+                  "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && d >= 1 && ldz >= d, "%s: bad shape rows=%lld n=%lld d=%d ldz=%lld", what,
+            (long long)table_rows, (long long)n, d, (long long)ldz);
+    REQUIRE(metric == CLANE_SILHOUETTE_EUCLIDEAN || metric == CLANE_SILHOUETTE_COSINE, "%s: unknown metric %d", what,
+            metric);
+    return CLANE_OK;
+}
+
+template <typename T, typename A>
+int silhouette_norms(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n, const A *mu,
+                     int32_t metric, A *nrm, void *stream) {
+    if (int rc = silhouette_check("silhouette_norms", table_rows, n, d, ldz, metric)) return rc;
+    if (n == 0) return CLANE_OK;
+    REQUIRE(order && mu && nrm && (Z || table_rows == 0), "silhouette_norms: null pointer");
+    const int64_t tiles = ceil_div(n, int64_t(kProjBM));
+    REQUIRE(tiles <= INT32_MAX, "silhouette_norms: %lld rows is too many for one launch", (long long)n);
+    silhouette_norms_kernel<T, A><<<unsigned(tiles), kBlock, 0, (hipStream_t)stream>>>(Z, table_rows, d, ldz, order, n, mu,
+                                                                                       metric, nrm);
+    return check_launch("silhouette_norms");
+}
+
+template <typename T, typename A>
+int silhouette_sums(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n,
+                    const int64_t *seg, int32_t K, const A *mu, const A *nrm, int32_t metric, int64_t p0, int64_t p1,
+                    double *S, void *stream) {
+    if (int rc = silhouette_check("silhouette_sums", table_rows, n, d, ldz, metric)) return rc;
+    REQUIRE(K >= 1, "silhouette_sums: K must be at least 1, got %d", K);
+    REQUIRE(p0 >= 0 && p0 <= p1 && p1 <= n, "silhouette_sums: positions [%lld, %lld) are not within [0, n = %lld]",
+            (long long)p0, (long long)p1, (long long)n);
+    if (p1 == p0) return CLANE_OK;
+    REQUIRE(order && seg && mu && nrm && S && (Z || table_rows == 0), "silhouette_sums: null pointer");
+    const int64_t row_tiles = ceil_div(p1 - p0, int64_t(kProjBM));
+    REQUIRE(row_tiles * K <= INT32_MAX, "silhouette_sums: %lld positions x %d clusters is too many for one launch",
+            (long long)(p1 - p0), K);
+    silhouette_sums_kernel<T, A><<<unsigned(row_tiles * K), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, order, n, seg, K, mu, nrm, metric, p0, p1, int(row_tiles), S);
+    return check_launch("silhouette_sums");
+}
+
 // ---- sparse rows (sparse_rows.h) ----------------------------------------------------------------------------------------
 inline int64_t csr_max_items(int64_t nnz) { return nnz > kCsrSegment ? 2 * (nnz / kCsrSegment) : 0; }
 
@@ -1889,5 +1932,22 @@ int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha,
                                                                     stats);
     return check_launch("tsne_step");
 }
+
+#define CLANE_SILHOUETTE_WRAPPERS(SUF, CT, T, AT)                                                                      \
+    int clane_silhouette_norms_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,    \
+                                     int64_t n, const AT *mu, int32_t metric, AT *nrm, void *stream) {                 \
+        return silhouette_norms<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, order, n, mu, metric, nrm,  \
+                                       stream);                                                                        \
+    }                                                                                                                  \
+    int clane_silhouette_sums_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,     \
+                                    int64_t n, const int64_t *seg, int32_t K, const AT *mu, const AT *nrm,             \
+                                    int32_t metric, int64_t p0, int64_t p1, double *S, void *stream) {                 \
+        return silhouette_sums<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, order, n, seg, K, mu, nrm,   \
+                                      metric, p0, p1, S, stream);                                                      \
+    }
+CLANE_SILHOUETTE_WRAPPERS(f32, float, float, float)
+CLANE_SILHOUETTE_WRAPPERS(f64, double, double, double)
+CLANE_SILHOUETTE_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_SILHOUETTE_WRAPPERS
 
 }  // extern "C"

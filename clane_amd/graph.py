@@ -588,7 +588,8 @@ class Graph(torch.utils.data.Dataset):
         return out
 
     def cluster(self, k=None, labels=None, vertices=None, restarts: int = 10, seed: int = 0, max_iter: int = 300,
-                table: str = "Z", return_assignments: bool = False) -> dict:
+                table: str = "Z", return_assignments: bool = False, silhouette: bool = False,
+                silhouette_metric: str = "euclidean", silhouette_points: Optional[int] = 65536) -> dict:
         """Node clustering of the CURRENT embeddings (extension): k-means, every restart at once on the GPU
         (cluster.py), the restart of lowest inertia reported.  With ``labels`` -- the three forms ``evaluate_labels``
         takes -- the labelled vertices are clustered, ``k`` defaults to the number of classes and the result carries
@@ -596,10 +597,30 @@ class Graph(torch.utils.data.Dataset):
         clustered into ``k`` clusters.  ``table="X"`` clusters the content embeddings instead.  Returns ``{"table",
         "clustered", "clusters", "restarts", "seed", "inertia", "iterations", "converged", "empty", "best_restart",
         "sizes", ...}``; with ``return_assignments`` also ``"vertices"`` and ``"assignments"`` (the best restart's
-        cluster per clustered vertex).  Several GPUs and a column division raise NotImplementedError."""
+        cluster per clustered vertex).  Several GPUs and a column division raise NotImplementedError.
+
+        ``silhouette=True`` scores the best restart (still chosen by inertia) without labels: ``silhouette`` (the mean
+        of the exact per-row silhouette under ``silhouette_metric``, csrc/silhouette.h; over at most ``silhouette_points``
+        vertices, sampled as ``layout`` samples, ``None``: all), ``silhouette_per_cluster``, ``calinski_harabasz`` and
+        ``davies_bouldin``; centres without rows are left out of all three.  ``k`` may be a sequence of counts: every one
+        is fitted with the same seeds and scored on the same sample, the result is that of the count with the highest mean
+        silhouette (ties to the smaller) and carries ``selection = {criterion, candidates: [{clusters, inertia,
+        silhouette, calinski_harabasz, davies_bouldin, empty}], chosen}``."""
         from .classify import index_classes, read_labels
         if k is None and labels is None:
             raise ValueError("cluster: give k, the number of clusters, or labels whose classes it defaults to")
+        ks, listed = [k], False
+        if isinstance(k, (list, tuple, range)) or (isinstance(k, torch.Tensor) and k.dim() > 0):
+            from .cluster import check_cluster_counts
+            ks, listed = check_cluster_counts(k)
+        silhouette = bool(silhouette) or listed
+        if silhouette:
+            from .cluster import SILHOUETTE_METRICS
+            if silhouette_metric not in SILHOUETTE_METRICS:
+                raise ValueError(f"cluster: silhouette_metric must be one of {SILHOUETTE_METRICS}, got {silhouette_metric!r}")
+            if silhouette_points is not None and (isinstance(silhouette_points, bool)
+                                                  or int(silhouette_points) != silhouette_points or silhouette_points < 2):
+                raise ValueError(f"cluster: silhouette_points must be an integer >= 2 or None, got {silhouette_points!r}")
         y = names = None
         if labels is not None:
             if isinstance(labels, (str, Path)):
@@ -618,14 +639,77 @@ class Graph(torch.utils.data.Dataset):
             vertices = list(range(len(self)))
         from .cluster import KMeans
         km = KMeans(self.engine(), max_iter=max_iter)
-        out = km.evaluate(vertices, k=k, y=y, n_classes=None if names is None else len(names), restarts=restarts,
-                          seed=seed, table=table)
-        if names is not None:
-            out["class_names"] = [str(c) for c in names]
-        if return_assignments:
-            out["vertices"] = [int(v) for v in vertices]
-            out["assignments"] = km.last_fit.assign[:, out["best_restart"]].tolist()
-        return out
+        sil = pick = None
+        if silhouette:
+            from .cluster import Silhouette, score_fit, select_clusters
+            from .layout import sample_vertices
+            sil = Silhouette(self.engine(), metric=silhouette_metric)
+            if silhouette_points is not None:                   # one sample for every candidate
+                pick, sampled = sample_vertices(len(vertices), int(silhouette_points), seed)
+                pick = pick if sampled else None
+
+        def run(k_one):
+            out = km.evaluate(vertices, k=k_one, y=y, n_classes=None if names is None else len(names), restarts=restarts,
+                              seed=seed, table=table)
+            if names is not None:
+                out["class_names"] = [str(c) for c in names]
+            if sil is not None:
+                tab, rows = km.table_and_rows(vertices, table)
+                out.update(score_fit(km, sil, tab, rows, km.last_fit, pick))
+                out["silhouette_metric"] = silhouette_metric
+                out["silhouette_scored"] = len(vertices) if pick is None else int(pick.numel())
+            if return_assignments:
+                out["vertices"] = [int(v) for v in vertices]
+                out["assignments"] = km.last_fit.assign[:, out["best_restart"]].tolist()
+            return out
+        return select_clusters(ks, run) if listed else run(ks[0])
+
+    def silhouette(self, partition=None, labels=None, vertices=None, table: str = "Z", metric: str = "euclidean",
+                   max_points: Optional[int] = 65536, seed: int = 0) -> dict:
+        """The exact silhouette of a partition of the CURRENT embeddings (extension; ``table="X"``: of the content):
+        ``partition`` -- one integer per vertex of ``vertices`` (default: all), a k-means assignment say -- or ``labels``
+        -- the three forms ``cluster`` takes; it scores how well the true classes separate in the embedding.  More than
+        ``max_points`` rows: the first ``max_points`` of a torch permutation seeded with ``seed``, sorted, as ``layout``
+        samples; ``None`` means all.  Returns ``{"mean", "per_cluster", "sizes", "n", "sampled", "metric", "table",
+        "clusters"}`` (``clusters``: the distinct partition values or class names, in the order of ``per_cluster`` and
+        ``sizes``).  The n x K sums of distances are formed on the GPU (csrc/silhouette.h), never the n x n distances.
+        Reads the engine's table where it lies and changes no state.  One GPU only."""
+        from .classify import index_classes, read_labels
+        from .cluster import Silhouette, dense_partition
+        from .layout import sample_vertices
+        if (partition is None) == (labels is None):
+            raise ValueError("silhouette: give partition, one integer per vertex, or labels -- one of the two")
+        if max_points is not None and (isinstance(max_points, bool) or int(max_points) != max_points or max_points < 2):
+            raise ValueError(f"silhouette: max_points must be an integer >= 2 or None, got {max_points!r}")
+        if labels is not None:
+            if isinstance(labels, (str, Path)):
+                vertices, y, names = read_labels(Path(labels), self.vertex_ids)
+            else:
+                if isinstance(labels, tuple) and len(labels) == 2:
+                    vertices, raw = list(labels[0]), list(labels[1])
+                else:
+                    raw = list(labels)
+                    vertices = list(range(len(self)))
+                if len(raw) != len(vertices):
+                    raise ValueError("silhouette: one class per labelled vertex")
+                y, names = index_classes([c.item() if isinstance(c, torch.Tensor) else c for c in raw])
+            own = torch.as_tensor(y, dtype=torch.int64).reshape(-1)
+            names = [str(c) for c in names]
+        else:
+            if vertices is None:
+                vertices = list(range(len(self)))
+            ids, own = dense_partition(torch.as_tensor(partition).reshape(-1).cpu())
+            if own.numel() != len(vertices):
+                raise ValueError(f"silhouette: one cluster per vertex, got {own.numel()} for {len(vertices)} vertices")
+            names = ids.tolist()
+        sil = Silhouette(self.engine(), metric=metric)
+        pool = torch.as_tensor(vertices, dtype=torch.int64).reshape(-1)
+        pick, sampled = sample_vertices(int(pool.numel()), int(pool.numel() if max_points is None else max_points), seed)
+        tab, rows = sil.table_and_rows(pool[pick], table)
+        res = sil.samples(tab, rows, own[pick], k=len(names))
+        return {"mean": res.mean, "per_cluster": [None if v != v else v for v in res.per_cluster.tolist()],
+                "sizes": res.sizes.tolist(), "n": int(pick.numel()), "sampled": bool(sampled), "metric": metric,
+                "table": table, "clusters": names}
 
     def reduce_content(self, dim: int, center: bool = True, whiten: bool = False, block_rows=None, transform=None):
         """Replace the content embeddings ``X`` (and ``d``) by their ``dim`` principal components (extension, reduce.py:

@@ -77,7 +77,9 @@ extern "C" {
                              *    + clane_tsne_sqdist_*, clane_tsne_affinities_f32, clane_tsne_symmetrize_f32,
                              *    clane_tsne_symmetrize_ws_len, clane_tsne_forces_f32, clane_tsne_step_f32 (2-D layout: exact
                              *    t-SNE of rows of the table -- all-pairs distances on the matrix cores, the perplexity
-                             *    search, the joint probabilities and the two kernels of an iteration) */
+                             *    search, the joint probabilities and the two kernels of an iteration)
+                             *    + clane_silhouette_norms_*, clane_silhouette_sums_* (silhouette of a partition of rows of
+                             *    the table: the n x K sums of distances on the matrix cores, never the n x n distances) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -923,6 +925,44 @@ int clane_tsne_symmetrize_f32(float *P, int64_t n, double *partials, void *strea
 int clane_tsne_forces_f32(const float *P, const float *Y, int64_t n, int32_t flags, float *F, void *stream);
 int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha, double momentum, double lr, double plogp,
                         float *V, float *G, float *Y_next, double *stats, void *stream);
+
+/* ---- silhouette of a partition (csrc/silhouette.h) -------------------------------------------------------------------------
+ * order [n] int32: table rows grouped by cluster; seg [K + 1] int64: cluster c is the positions [seg[c], seg[c + 1]) of
+ * `order` (clamped to [0, n]; an empty cluster is an empty range).  a_p = Z[order[p], 0:d) - mu, one subtraction in the
+ * accumulate type (fp32 for the _f32 and _bf16 tables, fp64 for _f64); an `order` entry outside [0, table_rows) is the row
+ * z = 0.  mu [d]: the caller's column mean for CLANE_SILHOUETTE_EUCLIDEAN (any shift leaves the distances unchanged and
+ * keeps the Gram trick's cancellation small), zeros for CLANE_SILHOUETTE_COSINE.  No allocation, no synchronisation, no
+ * atomics.
+ *
+ * silhouette_norms: nrm [n], accumulate type.  euclidean: |a_p|^2; cosine: 1 / sqrt(|a_p|^2), 0 for a zero row.  |a_p|^2 is
+ *   the dot a_p . a_p in the order of the library's one tile contraction (mfma_slice) -- the chain a_p . a_j runs through.
+ * silhouette_sums: S [p1 - p0, K] doubles, S[p - p0, c] = sum over j in cluster c of dist(p, j) for the positions p in
+ *   [p0, p1) -- the caller walks the positions in blocks, S is as large as a block.  nrm: what silhouette_norms left for
+ *   the same order, mu and metric.
+ *     euclidean: dist = sqrt(max(0, fma(-2, a_p . a_j, nrm_p + nrm_j))), the square root correctly rounded.  Two positions
+ *       whose table rows hold the same bits are at distance exactly 0.
+ *     cosine:    dist = max(0, 1 - ((a_p . a_j) nrm_p) nrm_j): a zero row is at distance 1 from every other position.
+ *   The term j == p is exactly 0.  An empty cluster's column is zeros.  Order of a sum: with q = j - seg[c], partial
+ *   (h, l) = ((q % 128) / 64, q % 16) adds its distances in double in ascending q; the 16 partials of one h are folded by the
+ *   xor butterfly over l (8, 4, 2, 1), the result is fold(0) + fold(1) -- a function of seg alone: S[p, c] has the same bits
+ *   for every [p0, p1) that holds p, and in every call. */
+#define CLANE_SILHOUETTE_EUCLIDEAN 0
+#define CLANE_SILHOUETTE_COSINE 1
+int clane_silhouette_norms_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n,
+                               const float *mu, int32_t metric, float *nrm, void *stream);
+int clane_silhouette_norms_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n,
+                               const double *mu, int32_t metric, double *nrm, void *stream);
+int clane_silhouette_norms_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,
+                                int64_t n, const float *mu, int32_t metric, float *nrm, void *stream);
+int clane_silhouette_sums_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n,
+                              const int64_t *seg, int32_t K, const float *mu, const float *nrm, int32_t metric, int64_t p0,
+                              int64_t p1, double *S, void *stream);
+int clane_silhouette_sums_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order, int64_t n,
+                              const int64_t *seg, int32_t K, const double *mu, const double *nrm, int32_t metric,
+                              int64_t p0, int64_t p1, double *S, void *stream);
+int clane_silhouette_sums_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *order,
+                               int64_t n, const int64_t *seg, int32_t K, const float *mu, const float *nrm, int32_t metric,
+                               int64_t p0, int64_t p1, double *S, void *stream);
 
 #ifdef __cplusplus
 }
