@@ -115,7 +115,8 @@ def embedding(args):
             arrivals_root = Path(args.data_root) / arrivals_root
         arrivals = induct.read_arrivals(arrivals_root, read_vertex_ids(Path(args.data_root)), None)
     # optional section (extension): layout: {perplexity: 30, max_points: 20000, max_iter: 1000, seed: 0, labels: Y,
-    # baseline: true} -- the 2-D t-SNE picture of the embeddings the run ends with (layout.py); checked before the graph loads
+    # baseline: true, method: exact | neighbours, neighbours: K} -- the 2-D t-SNE picture of the embeddings the run ends
+    # with (layout.py); checked before the graph loads
     layout_cfg = layout_labels = None
     if isinstance(hparams, dict) and "layout" in hparams:
         from . import layout as layout_mod
@@ -322,7 +323,8 @@ def embedding(args):
 
     if layout_cfg is not None:                      # the picture of the embeddings the run ends with
         from . import layout as layout_mod
-        kw = {key: layout_cfg[key] for key in ("perplexity", "max_points", "max_iter", "seed")}
+        kw = {key: layout_cfg[key] for key in ("perplexity", "max_points", "max_iter", "seed", "method", "neighbours")
+              if key in layout_cfg}
         tables = {"Z": g.layout(table="Z", labels=layout_labels, **kw)}
         if layout_cfg["baseline"]:
             tables["X"] = g.layout(table="X", labels=layout_labels, **kw)

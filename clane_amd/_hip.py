@@ -154,6 +154,15 @@ SIGNATURES["clane_tsne_symmetrize_f32"] = (C.c_int, [_p, _i64, _p, _p])
 SIGNATURES["clane_tsne_forces_f32"] = (C.c_int, [_p, _p, _i64, _i32, _p, _p])
 SIGNATURES["clane_tsne_step_f32"] = (
     C.c_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p])
+KNN_MAX_K = 192                     # CLANE_KNN_MAX_K; neighbour-sparse 2-D layout (csrc/tsne_nn.h)
+TSNE_NN_MAX_POINTS = 1 << 20        # CLANE_TSNE_NN_MAX_POINTS
+for _s in ("f32", "bf16"):
+    SIGNATURES[f"clane_knn_sqdist_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _p, _p])
+SIGNATURES["clane_tsne_nn_affinities_f32"] = (C.c_int, [_p, _p, _i64, _i32, C.c_float, _p, _p, _p])
+SIGNATURES["clane_tsne_nn_plogp_f32"] = (C.c_int, [_p, _p, _i64, _i64, _p, _p])
+SIGNATURES["clane_tsne_nn_attract_f32"] = (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p])
+SIGNATURES["clane_tsne_repulse_f32"] = (C.c_int, [_p, _i64, _p, _p])
 SILHOUETTE_METRICS = {"euclidean": 0, "cosine": 1}      # CLANE_SILHOUETTE_*; silhouette (csrc/silhouette.h)
 for _s in ("f32", "f64", "bf16"):
     SIGNATURES[f"clane_silhouette_norms_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p])
@@ -645,6 +654,29 @@ class KernelBackend(abc.ABC):
     def tsne_step(self, F, Y, alpha: float, momentum: float, lr: float, plogp: float, V, G, Y_next, stats):
         """scikit-learn's gradient-descent update from the force sums; stats (float64 [4]) = KL, |g|, S, sum l."""
         raise NotImplementedError(f"{type(self).__name__} has no tsne_step")
+
+    # neighbour-sparse 2-D layout (layout.py): optional in the same way -- KNeighbours and NeighbourTSNE are the only
+    # callers.  ids int32 / sqdist, p float32 [n, k]; the joint P as CSR (rowptr int64 [n + 1], cols int32, val float32).
+    def knn_sqdist(self, Z, d: int, rows, mu, sq, ids, sqdist, n_slabs: int = 1, cand_ids=None, cand_sqdist=None):
+        """ids[i] = the positions in ``rows`` of the k nearest other listed rows of row i (distance ascending, ties by
+        position), sqdist[i] their squared distances: tsne_sqdist's bits; -1 / +inf past the n - 1 other rows."""
+        raise NotImplementedError(f"{type(self).__name__} has no knn_sqdist")
+
+    def tsne_nn_affinities(self, sqdist, ids, perplexity: float, p, beta):
+        """p[i] = the conditional affinities of row i over its k neighbours at the beta_i of the given perplexity."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_nn_affinities")
+
+    def tsne_nn_plogp(self, rowptr, val, row_plogp):
+        """row_plogp[i] (float64) = sum p ln p over CSR row i, in a fixed order."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_nn_plogp")
+
+    def tsne_nn_attract(self, rowptr, cols, val, Y, F, kl: bool = True):
+        """Columns 0, 1 (attraction) and 5 (with ``kl`` sum_j P_ij log1p(|y_i - y_j|^2), else 0) of F from the CSR rows."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_nn_attract")
+
+    def tsne_repulse(self, Y, F):
+        """Columns 2, 3 (repulsion) and 4 (sum_{j != i} q_ij) of F over all pairs."""
+        raise NotImplementedError(f"{type(self).__name__} has no tsne_repulse")
 
     # silhouette (cluster.py): optional in the same way -- Silhouette is the only caller.  order: TABLE ROWS (int32) grouped
     # by cluster, seg int64 [K + 1] the clusters' starts in it; mu and nrm in the accumulate dtype.
@@ -1534,6 +1566,83 @@ class HipKernels(KernelBackend):
                      _vec(F, f32, "F"), _vec(Y, f32, "Y"), n, float(alpha), float(momentum), float(lr), float(plogp),
                      _vec(V, f32, "V"), _vec(G, f32, "G"), _vec(Y_next, f32, "Y_next"), _vec(stats, torch.float64, "stats"),
                      self._stream(Y))
+
+    # -- neighbour-sparse 2-D layout ------------------------------------------------------------
+    @staticmethod
+    def _nn_lists(what: str, n: int, **arrays) -> int:
+        k = None
+        for name, t in arrays.items():
+            want = torch.int32 if name.endswith("ids") else torch.float32
+            if t.dim() != 2 or t.shape[0] != n or t.dtype != want or not t.is_contiguous() or (k is not None
+                                                                                              and t.shape[1] != k):
+                raise ValueError(f"{what}: {name} must be a contiguous {want} [{n}, k], got {tuple(t.shape)} {t.dtype}")
+            k = int(t.shape[1])
+        if not 1 <= k <= KNN_MAX_K:
+            raise ValueError(f"{what}: k must be in [1, {KNN_MAX_K}], got {k}")
+        return k
+
+    def knn_sqdist(self, Z, d: int, rows, mu, sq, ids, sqdist, n_slabs: int = 1, cand_ids=None, cand_sqdist=None):
+        zp, ldz = _mat(Z, "Z")
+        if Z.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"knn_sqdist: float32 and bfloat16 tables, not {Z.dtype}")
+        n, n_slabs = int(rows.numel()), int(n_slabs)
+        if n > TSNE_NN_MAX_POINTS:
+            raise ValueError(f"knn_sqdist: n = {n} exceeds {TSNE_NN_MAX_POINTS} rows")
+        k = self._nn_lists("knn_sqdist", n, ids=ids, sqdist=sqdist)
+        if mu.numel() != d or sq.numel() != n:
+            raise ValueError(f"knn_sqdist: mu needs d = {d} entries and sq one per listed row ({n})")
+        if n_slabs < 1:
+            raise ValueError(f"knn_sqdist: n_slabs must be at least 1, got {n_slabs}")
+        ci = cd = None
+        if n_slabs > 1:
+            if cand_ids is None or cand_sqdist is None or cand_ids.numel() != n * n_slabs * k \
+                    or cand_sqdist.numel() != n * n_slabs * k:
+                raise ValueError(f"knn_sqdist: n_slabs = {n_slabs} needs cand_ids and cand_sqdist of n * n_slabs * k = "
+                                 f"{n * n_slabs * k} elements")
+            ci, cd = _vec(cand_ids, torch.int32, "cand_ids"), _vec(cand_sqdist, torch.float32, "cand_sqdist")
+        f32 = torch.float32
+        self._invoke(self._fn("clane_knn_sqdist", Z.dtype), "clane_knn_sqdist",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(mu, f32, "mu"), _vec(sq, f32, "sq"),
+                     k, n_slabs, cd, ci, sqdist.data_ptr(), ids.data_ptr(), self._stream(ids))
+
+    def tsne_nn_affinities(self, sqdist, ids, perplexity: float, p, beta):
+        n = int(sqdist.shape[0])
+        self._nn_lists("tsne_nn_affinities", n, sqdist=sqdist, ids=ids, p=p)
+        if beta.numel() != n:
+            raise ValueError(f"tsne_nn_affinities: beta needs {n} entries")
+        self._invoke(self.lib.clane_tsne_nn_affinities_f32, "clane_tsne_nn_affinities",
+                     sqdist.data_ptr(), ids.data_ptr(), n, int(sqdist.shape[1]), float(perplexity), p.data_ptr(),
+                     _vec(beta, torch.float32, "beta"), self._stream(p))
+
+    @staticmethod
+    def _nn_csr(what: str, rowptr, cols, val) -> tuple:
+        n, nnz = int(rowptr.numel()) - 1, int(val.numel())
+        if n < 1 or (cols is not None and cols.numel() != nnz):
+            raise ValueError(f"{what}: rowptr needs n + 1 >= 2 entries, cols and val one per non-zero")
+        return n, nnz
+
+    def tsne_nn_plogp(self, rowptr, val, row_plogp):
+        n, nnz = self._nn_csr("tsne_nn_plogp", rowptr, None, val)
+        if row_plogp.numel() != n:
+            raise ValueError(f"tsne_nn_plogp: row_plogp needs {n} doubles")
+        self._invoke(self.lib.clane_tsne_nn_plogp_f32, "clane_tsne_nn_plogp",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(val, torch.float32, "val") if nnz else None, n, nnz,
+                     _vec(row_plogp, torch.float64, "row_plogp"), self._stream(row_plogp))
+
+    def tsne_nn_attract(self, rowptr, cols, val, Y, F, kl: bool = True):
+        n, nnz = self._nn_csr("tsne_nn_attract", rowptr, cols, val)
+        self._tsne_points(n, "tsne_nn_attract", Y=Y, F=F)
+        f32 = torch.float32
+        self._invoke(self.lib.clane_tsne_nn_attract_f32, "clane_tsne_nn_attract",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(cols, torch.int32, "cols") if nnz else None,
+                     _vec(val, f32, "val") if nnz else None, _vec(Y, f32, "Y"), n, nnz, TSNE_FORCES_KL if kl else 0,
+                     _vec(F, f32, "F"), self._stream(F))
+
+    def tsne_repulse(self, Y, F):
+        n = int(Y.shape[0])
+        self._tsne_points(n, "tsne_repulse", Y=Y, F=F)
+        self._invoke(self.lib.clane_tsne_repulse_f32, "clane_tsne_repulse",
+                     _vec(Y, torch.float32, "Y"), n, _vec(F, torch.float32, "F"), self._stream(F))
 
     # -- silhouette -------------------------------------------------------------------------
     def _silhouette_args(self, what: str, Z, d: int, order, mu, metric: str, nrm):

@@ -25,6 +25,7 @@
 #include "spmm_update.h"
 #include "silhouette.h"
 #include "tsne.h"
+#include "tsne_nn.h"
 
 namespace {
 
@@ -1255,6 +1256,42 @@ int tsne_sqdist(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const in
     return check_launch("tsne_sqdist");
 }
 
+// ---- neighbour-sparse 2-D layout (tsne_nn.h) --------------------------------------------------------------------------------
+template <typename T>
+int knn_sqdist(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const float *mu,
+               float *sq, int32_t k, int32_t n_slabs, float *cand_sqdist, int32_t *cand_ids, float *sqdist, int32_t *ids,
+               void *stream) {
+    static_assert(kKnnMaxK == CLANE_KNN_MAX_K && kTsneNnMaxPoints == CLANE_TSNE_NN_MAX_POINTS, "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && n <= kTsneNnMaxPoints && d > 0 && ldz >= d,
+            "knn_sqdist: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d, (long long)ldz);
+    REQUIRE(k >= 1 && k <= CLANE_KNN_MAX_K, "knn_sqdist: k must be in [1, %d], got %d", CLANE_KNN_MAX_K, k);
+    REQUIRE(n_slabs >= 1 && n_slabs <= 65536, "knn_sqdist: n_slabs must be in [1, 65536], got %d", n_slabs);
+    if (n == 0) return CLANE_OK;
+    REQUIRE(rows && mu && sq && sqdist && ids && (Z || table_rows == 0), "knn_sqdist: null pointer");
+    REQUIRE(n_slabs == 1 || (cand_sqdist && cand_ids), "knn_sqdist: n_slabs > 1 needs the candidate workspace");
+    const int mi = knn_tile_mi(k);
+    const int64_t q_tiles = ceil_div(n, int64_t(32 * mi));
+    const int64_t blocks = q_tiles * n_slabs;
+    REQUIRE(blocks <= INT32_MAX, "knn_sqdist: %lld rows x %d slabs is too many for one launch", (long long)n, n_slabs);
+    const int64_t tiles_total = ceil_div(n, int64_t(kProjBN));
+    const int64_t tiles_per_slab = ceil_div(tiles_total, int64_t(n_slabs));
+    float *out_d = n_slabs == 1 ? sqdist : cand_sqdist;     // one slab: its lists are the result
+    int32_t *out_i = n_slabs == 1 ? ids : cand_ids;
+    tsne_sqnorm_kernel<T><<<unsigned(ceil_div(n, int64_t(kBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, rows, n, mu, sq);
+    auto launch = [&]<int MI>() {
+        knn_sqdist_kernel<T, MI><<<unsigned(blocks), kBlock, knn_list_bytes(MI, k), (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, n, mu, sq, k, n_slabs, q_tiles, tiles_per_slab, out_d, out_i);
+    };
+    if (mi == 4) launch.template operator()<4>();
+    else if (mi == 2) launch.template operator()<2>();
+    else launch.template operator()<1>();
+    if (n_slabs > 1)
+        knn_merge_kernel<<<unsigned(ceil_div(n, int64_t(kWavesPerBlock))), kBlock, 0, (hipStream_t)stream>>>(
+            cand_sqdist, cand_ids, n, n_slabs, k, sqdist, ids);
+    return check_launch("knn_sqdist");
+}
+
 // ---- silhouette (silhouette.h) ------------------------------------------------------------------------------------------
 inline int silhouette_check(const char *what, int64_t table_rows, int64_t n, int32_t d, int64_t ldz, int32_t metric) {
     static_assert(kSilEuclidean == CLANE_SILHOUETTE_EUCLIDEAN && kSilCosine == CLANE_SILHOUETTE_COSINE,
@@ -1925,12 +1962,63 @@ int clane_tsne_forces_f32(const float *P, const float *Y, int64_t n, int32_t fla
 }
 int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha, double momentum, double lr, double plogp,
                         float *V, float *G, float *Y_next, double *stats, void *stream) {
-    REQUIRE(n >= 1 && n <= kTsneMaxPoints, "tsne_step: n must be in [1, %d], got %lld", kTsneMaxPoints, (long long)n);
+    REQUIRE(n >= 1 && n <= kTsneNnMaxPoints, "tsne_step: n must be in [1, %d], got %lld", kTsneNnMaxPoints, (long long)n);
     REQUIRE(F && Y && V && G && Y_next && stats, "tsne_step: null pointer");
     REQUIRE(Y != Y_next, "tsne_step: Y must not be the array being written");
     tsne_step_kernel<<<1, kTsneStepBlock, 0, (hipStream_t)stream>>>(F, Y, n, alpha, momentum, lr, plogp, V, G, Y_next,
                                                                     stats);
     return check_launch("tsne_step");
+}
+
+int clane_knn_sqdist_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                         const float *mu, float *sq, int32_t k, int32_t n_slabs, float *cand_sqdist, int32_t *cand_ids,
+                         float *sqdist, int32_t *ids, void *stream) {
+    return knn_sqdist<float>(Z, table_rows, d, ldz, rows, n, mu, sq, k, n_slabs, cand_sqdist, cand_ids, sqdist, ids, stream);
+}
+int clane_knn_sqdist_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          const float *mu, float *sq, int32_t k, int32_t n_slabs, float *cand_sqdist, int32_t *cand_ids,
+                          float *sqdist, int32_t *ids, void *stream) {
+    return knn_sqdist<bf16_t>(reinterpret_cast<const bf16_t *>(Z), table_rows, d, ldz, rows, n, mu, sq, k, n_slabs,
+                              cand_sqdist, cand_ids, sqdist, ids, stream);
+}
+int clane_tsne_nn_affinities_f32(const float *sqdist, const int32_t *ids, int64_t n, int32_t k, float perplexity, float *p,
+                                 float *beta, void *stream) {
+    REQUIRE(n >= 2 && n <= kTsneNnMaxPoints, "tsne_nn_affinities: n must be in [2, %d], got %lld", kTsneNnMaxPoints,
+            (long long)n);
+    REQUIRE(k >= 1 && k <= CLANE_KNN_MAX_K, "tsne_nn_affinities: k must be in [1, %d], got %d", CLANE_KNN_MAX_K, k);
+    REQUIRE(perplexity > 0.f && perplexity < float(k), "tsne_nn_affinities: perplexity %g is not in (0, k = %d)",
+            double(perplexity), k);
+    REQUIRE(sqdist && ids && p && beta, "tsne_nn_affinities: null pointer");
+    tsne_nn_affinities_kernel<<<unsigned(ceil_div(n, int64_t(kNnRowsPerBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        sqdist, ids, n, k, perplexity, p, beta);
+    return check_launch("tsne_nn_affinities");
+}
+int clane_tsne_nn_plogp_f32(const int64_t *rowptr, const float *val, int64_t n, int64_t nnz, double *row_plogp,
+                            void *stream) {
+    REQUIRE(n >= 1 && n <= kTsneNnMaxPoints && nnz >= 0, "tsne_nn_plogp: bad shape n=%lld nnz=%lld", (long long)n,
+            (long long)nnz);
+    REQUIRE(rowptr && row_plogp && (val || nnz == 0), "tsne_nn_plogp: null pointer");
+    tsne_nn_plogp_kernel<<<unsigned(ceil_div(n, int64_t(kNnRowsPerBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        rowptr, val, n, nnz, row_plogp);
+    return check_launch("tsne_nn_plogp");
+}
+int clane_tsne_nn_attract_f32(const int64_t *rowptr, const int32_t *cols, const float *val, const float *Y, int64_t n,
+                              int64_t nnz, int32_t flags, float *F, void *stream) {
+    REQUIRE(n >= 1 && n <= kTsneNnMaxPoints && nnz >= 0, "tsne_nn_attract: bad shape n=%lld nnz=%lld", (long long)n,
+            (long long)nnz);
+    REQUIRE((flags & ~CLANE_TSNE_FORCES_KL) == 0, "tsne_nn_attract: unknown flags %d", flags);
+    REQUIRE(rowptr && Y && F && ((cols && val) || nnz == 0), "tsne_nn_attract: null pointer");
+    REQUIRE((const void *)Y != (const void *)F, "tsne_nn_attract: Y must not be the array being written");
+    tsne_nn_attract_kernel<<<unsigned(ceil_div(n, int64_t(kNnRowsPerBlock))), kBlock, 0, (hipStream_t)stream>>>(
+        rowptr, cols, val, Y, n, nnz, flags & CLANE_TSNE_FORCES_KL, F);
+    return check_launch("tsne_nn_attract");
+}
+int clane_tsne_repulse_f32(const float *Y, int64_t n, float *F, void *stream) {
+    REQUIRE(n >= 1 && n <= kTsneNnMaxPoints, "tsne_repulse: n must be in [1, %d], got %lld", kTsneNnMaxPoints, (long long)n);
+    REQUIRE(Y && F, "tsne_repulse: null pointer");
+    REQUIRE((const void *)Y != (const void *)F, "tsne_repulse: Y must not be the array being written");
+    tsne_repulse_kernel<<<unsigned(ceil_div(n, int64_t(kRepulseRowsPerBlock))), kBlock, 0, (hipStream_t)stream>>>(Y, n, F);
+    return check_launch("tsne_repulse");
 }
 
 #define CLANE_SILHOUETTE_WRAPPERS(SUF, CT, T, AT)                                                                      \

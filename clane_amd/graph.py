@@ -773,7 +773,7 @@ class Graph(torch.utils.data.Dataset):
         return pca.transform_table(eng, table, vertices).cpu(), pca
 
     def layout(self, table: str = "Z", vertices=None, max_points: int = 20000, seed: int = 0, labels=None,
-               **tsne_kwargs):
+               method: str = "exact", neighbours=None, **tsne_kwargs):
         """``(Y [n, 2] on the host, the laid-out vertex indices, info)``: the exact t-SNE layout (extension, layout.py:
         distances, perplexity search and every iteration on the GPU) of the CURRENT embeddings (``table="X"``: of the
         content) of ``vertices`` (default: all).  More than ``max_points`` of them: the first ``max_points`` of a torch
@@ -781,9 +781,18 @@ class Graph(torch.utils.data.Dataset):
         ``id<TAB>class`` lines, one class per vertex of the graph, or ``(vertices, classes)`` -- adds ``"classes"`` (per
         laid-out vertex, None where unlabelled) and ``"neighbour_agreement"`` (k = 5, over the labelled ones) to
         ``info``, next to ``n, sampled, table, perplexity, iterations, kl, kl_init, grad_norm, kl_trace``.
-        ``tsne_kwargs`` go to ``layout.TSNE``.  Reads the engine's table where it lies and changes no state.  One GPU only."""
+        ``tsne_kwargs`` go to ``layout.TSNE``.  Reads the engine's table where it lies and changes no state.  One GPU only.
+
+        ``method="neighbours"`` lays out up to 2^20 points (``layout.NeighbourTSNE``: P on every point's ``neighbours``
+        nearest neighbours -- None: ``3 * perplexity`` -- and the repulsion exact); ``info`` then also carries ``method``,
+        ``neighbours`` and ``nnz``.  ``"exact"`` keeps all of ``P [n, n]`` and stops at 65 536 points."""
         from .classify import read_labels
-        from .layout import MIN_POINTS, TSNE, neighbour_agreement, sample_vertices
+        from .layout import METHODS, MIN_POINTS, TSNE, NeighbourTSNE, neighbour_agreement, sample_vertices
+        if method not in METHODS:
+            raise ValueError(f"layout: method must be one of {list(METHODS)}, got {method!r}")
+        if neighbours is not None and method != "neighbours":
+            raise ValueError(f"layout: neighbours = {neighbours!r} needs method=\"neighbours\" (method {method!r} keeps "
+                             f"all of P)")
         if isinstance(max_points, bool) or int(max_points) != max_points or int(max_points) < MIN_POINTS:
             raise ValueError(f"layout: max_points must be an integer >= {MIN_POINTS}, got {max_points!r}")
         cls_of = None
@@ -802,7 +811,10 @@ class Graph(torch.utils.data.Dataset):
         pool = torch.arange(len(self)) if vertices is None else torch.as_tensor(vertices, dtype=torch.int64).reshape(-1)
         pick, sampled = sample_vertices(int(pool.numel()), int(max_points), seed)
         chosen = pool[pick]
-        tsne = TSNE(self.engine(), **tsne_kwargs)
+        if method == "neighbours":
+            tsne = NeighbourTSNE(self.engine(), neighbours=neighbours, **tsne_kwargs)
+        else:
+            tsne = TSNE(self.engine(), **tsne_kwargs)
         tsne.check_points(int(chosen.numel()))                  # before the table is touched
         tab, rows = tsne.table_and_rows(chosen, table)
         fit = tsne.fit(tab, rows, seed=seed)
@@ -810,6 +822,8 @@ class Graph(torch.utils.data.Dataset):
         info = {"n": int(chosen.numel()), "sampled": bool(sampled), "table": table, "perplexity": tsne.perplexity,
                 "iterations": fit.iterations, "kl": fit.kl, "kl_init": fit.kl_init, "grad_norm": fit.grad_norm,
                 "kl_trace": list(fit.kl_trace)}
+        if method == "neighbours":
+            info.update(method=method, neighbours=fit.neighbours, nnz=fit.nnz)
         if cls_of is not None:
             classes = [cls_of.get(int(v)) for v in chosen.tolist()]
             known = [i for i, c in enumerate(classes) if c is not None]
@@ -818,6 +832,23 @@ class Graph(torch.utils.data.Dataset):
             info["neighbour_agreement"] = (neighbour_agreement(Y[known], [index[classes[i]] for i in known], k=5)
                                            if len(known) > 5 else None)
         return Y, chosen, info
+
+    def neighbours(self, k: int, vertices=None, table: str = "Z"):
+        """``(indices [m, k] int64, distances [m, k] float32)`` on the host: for every vertex of ``vertices`` (default:
+        all) its ``k`` nearest OTHER vertices of ``vertices`` in the CURRENT embeddings (``table="X"``: in the content),
+        as vertex indices, nearest first, ties to the earlier place in ``vertices``; squared Euclidean distances of the
+        rows centred by their column mean -- the distances of ``layout`` (extension, layout.KNeighbours: distances and
+        selection in one kernel, never the m x m matrix).  With ``k >= m`` the places past the ``m - 1`` others hold
+        ``-1`` and ``inf``.  Euclidean only.  Reads the engine's table where it lies and changes no state.  One GPU only."""
+        from .classify import table_and_rows
+        from .layout import KNeighbours
+        pool = torch.arange(len(self)) if vertices is None else torch.as_tensor(vertices, dtype=torch.int64).reshape(-1)
+        KNeighbours.check(int(pool.numel()), k)                  # before the table is touched
+        knn = KNeighbours(self.engine())
+        tab, rows = table_and_rows(knn.eng, pool, table)
+        ids, sqdist = knn.search(tab, rows, k)
+        ids = ids.cpu().to(torch.int64)
+        return torch.where(ids >= 0, pool[ids.clamp(min=0)], ids), sqdist.cpu()
 
     def _build_P_bilinear(self, eng, similarity) -> None:
         """P of an AsymmertricSimilarity on the engine, from the module's weights as they are NOW (copied to the device on

@@ -79,7 +79,12 @@ extern "C" {
                              *    t-SNE of rows of the table -- all-pairs distances on the matrix cores, the perplexity
                              *    search, the joint probabilities and the two kernels of an iteration)
                              *    + clane_silhouette_norms_*, clane_silhouette_sums_* (silhouette of a partition of rows of
-                             *    the table: the n x K sums of distances on the matrix cores, never the n x n distances) */
+                             *    the table: the n x K sums of distances on the matrix cores, never the n x n distances)
+                             *    + clane_knn_sqdist_*, clane_tsne_nn_affinities_f32, clane_tsne_nn_plogp_f32,
+                             *    clane_tsne_nn_attract_f32, clane_tsne_repulse_f32 (neighbour-sparse 2-D layout: the k
+                             *    nearest listed rows of every listed row with the selection fused into the distances, P
+                             *    on those neighbours only, the repulsion exact; clane_tsne_step_f32 takes up to
+                             *    CLANE_TSNE_NN_MAX_POINTS points) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -911,7 +916,7 @@ int clane_csr_row_sums_f32(const int64_t *rowptr, const float *val, int64_t n_ro
  *   gain += 0.2 where v g < 0, else gain *= 0.8, floor 0.01; v = momentum v - lr gain g; Y_next = Y + v.  V and G are
  *   updated in place; Y_next must not be Y.  stats [4] doubles: KL = plogp + sum_i F[i, 5] + ln S (plogp: the sum of
  *   tsne_symmetrize's partials; valid at alpha = 1 and when the forces were taken with CLANE_TSNE_FORCES_KL), |g|, S,
- *   sum_i F[i, 5]. */
+ *   sum_i F[i, 5].  tsne_step alone takes n up to CLANE_TSNE_NN_MAX_POINTS: the neighbour-sparse path below shares it. */
 #define CLANE_TSNE_MAX_POINTS 65536
 #define CLANE_TSNE_FORCES_KL 1
 #define CLANE_TSNE_FORCES_CACHED 2
@@ -925,6 +930,46 @@ int clane_tsne_symmetrize_f32(float *P, int64_t n, double *partials, void *strea
 int clane_tsne_forces_f32(const float *P, const float *Y, int64_t n, int32_t flags, float *F, void *stream);
 int clane_tsne_step_f32(const float *F, const float *Y, int64_t n, double alpha, double momentum, double lr, double plogp,
                         float *V, float *G, float *Y_next, double *stats, void *stream);
+
+/* ---- neighbour-sparse 2-D layout (csrc/tsne_nn.h) ---------------------------------------------------------------------------
+ * t-SNE with P kept on every point's k nearest neighbours and the repulsion exact: nothing is n x n, 2 <= n <=
+ * CLANE_TSNE_NN_MAX_POINTS.  No allocation, no synchronisation, no atomics; the order of every sum is a function of n (and
+ * of k, or of the CSR) alone: two calls give the same bits.
+ *
+ * knn_sqdist: for every listed row i its k nearest OTHER listed rows: ids [n, k] int32 -- positions in `rows` -- and
+ *   sqdist [n, k] fp32, by distance ascending, ties by position ascending.  The distances are tsne_sqdist's own (the same
+ *   centring, norms, contraction and expression): sqdist[i, r] is bit for bit D[i, ids[i, r]] of the exact path.  Places
+ *   past the n - 1 other rows hold id -1 and +inf.  1 <= k <= CLANE_KNN_MAX_K.  sq [n] fp32: workspace, left filled with
+ *   the squared norms.  The candidate positions are cut into n_slabs slabs of whole 128-position tiles, each slab's lists
+ *   go to cand_sqdist / cand_ids [n, n_slabs, k] and a merge kernel combines them (n_slabs = 1: neither is read and both
+ *   may be null); the result does not depend on n_slabs.  A workgroup keeps the lists of 128 (k <= 40), 64 (k <= 96) or
+ *   32 queries in LDS.
+ * tsne_nn_affinities: tsne_affinities' perplexity search over the k distances of every row (the same steps, tolerance,
+ *   shift by the row's minimum, fp32 partials added in double): p [n, k] the conditionals, 0 where ids < 0; beta [n].
+ *   One wave per row: lane l adds the places l, l + 64, l + 128 in order, the lanes by the xor butterfly.
+ *   0 < perplexity < k.
+ * tsne_nn_plogp: row_plogp[i] (double) = sum p ln p over row i of a CSR (rowptr int64 [n + 1], val fp32 [nnz]): lane l of
+ *   the row's wave adds the entries l, l + 64, .. in column order, the lanes by the xor butterfly.
+ * tsne_nn_attract: F[i, 0:2] = sum_j P_ij q_ij (y_i - y_j) over the entries of CSR row i (cols int32, a column outside
+ *   [0, n) is skipped) and, with CLANE_TSNE_FORCES_KL, F[i, 5] = sum_j P_ij log1p(|y_i - y_j|^2) (0 without); the other
+ *   columns of F [n, 6] are left alone.  One wave per row however long, in the order of tsne_nn_plogp.
+ * tsne_repulse: F[i, 2:4] = sum_j q_ij^2 (y_i - y_j), F[i, 4] = sum_{j != i} q_ij over ALL j, Y through LDS, in
+ *   tsne_forces' order; the other columns are left alone.  attract + repulse fill what tsne_step reads. */
+#define CLANE_KNN_MAX_K 192
+#define CLANE_TSNE_NN_MAX_POINTS 1048576
+int clane_knn_sqdist_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                         const float *mu, float *sq, int32_t k, int32_t n_slabs, float *cand_sqdist, int32_t *cand_ids,
+                         float *sqdist, int32_t *ids, void *stream);
+int clane_knn_sqdist_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                          const float *mu, float *sq, int32_t k, int32_t n_slabs, float *cand_sqdist, int32_t *cand_ids,
+                          float *sqdist, int32_t *ids, void *stream);
+int clane_tsne_nn_affinities_f32(const float *sqdist, const int32_t *ids, int64_t n, int32_t k, float perplexity, float *p,
+                                 float *beta, void *stream);
+int clane_tsne_nn_plogp_f32(const int64_t *rowptr, const float *val, int64_t n, int64_t nnz, double *row_plogp,
+                            void *stream);
+int clane_tsne_nn_attract_f32(const int64_t *rowptr, const int32_t *cols, const float *val, const float *Y, int64_t n,
+                              int64_t nnz, int32_t flags, float *F, void *stream);
+int clane_tsne_repulse_f32(const float *Y, int64_t n, float *F, void *stream);
 
 /* ---- silhouette of a partition (csrc/silhouette.h) -------------------------------------------------------------------------
  * order [n] int32: table rows grouped by cluster; seg [K + 1] int64: cluster c is the positions [seg[c], seg[c + 1]) of
