@@ -872,9 +872,7 @@ class HipKernels(KernelBackend):
         on the host (the engine does): without it the size check of `stats` reads it back from the device, which
         blocks the host on everything queued before this call."""
         zp, ldz = _mat(Z, "Z")
-        n_items = item_e0.numel()
-        if n_items % items_per_block or any(t.numel() != n_items for t in (item_len, item_slot, item_row)):
-            raise ValueError("edge_score_class: the item arrays must hold whole blocks of items_per_block items")
+        n_blocks = self._item_blocks("edge_score_class", items_per_block, item_e0, item_len, item_slot, item_row)
         if fuse_softmax and (stats is None or stats.numel() < 2 * (int(slot_ptr[-1]) if n_slots is None else n_slots)):
             raise ValueError("edge_score_class: stats needs 2 elements per slot")
         acc = acc_dtype(Z.dtype)
@@ -882,7 +880,7 @@ class HipKernels(KernelBackend):
             _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
             _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
             _vec(item_slot, torch.int32, "item_slot"), _vec(item_row, torch.int32, "item_row"),
-            n_items // items_per_block, items_per_block, _vec(class_rows, torch.int32, "class_rows"),
+            n_blocks, items_per_block, _vec(class_rows, torch.int32, "class_rows"),
             _vec(slot_ptr, torch.int64, "slot_ptr"), class_rows.numel(), row0, zp, ldz, d, mode, _ptr(sums2), _ptr(sq),
             _vec(scores, acc, "scores"),
             (SCORE_FUSE_SOFTMAX | ((max(1, min(255, int(row_parts))) & 0xff) << 8)) if fuse_softmax else 0,
@@ -906,32 +904,61 @@ class HipKernels(KernelBackend):
     def _sq_arg(sq: Optional[torch.Tensor], dtype: torch.dtype):
         return None if sq is None else _vec(sq, acc_dtype(dtype), "sq_a")
 
+    @staticmethod
+    def _tables(name: str, Z_old, X, Z_new, f32_only: bool = False):
+        """The three tables of a K3 call, checked: (zo, ldz, xp, ldx, zn, ldo)."""
+        zo, ldz = _mat(Z_old, "Z_old")
+        xp, ldx = _mat(X, "X")
+        zn, ldo = _mat(Z_new, "Z_new")
+        if f32_only and not (Z_old.dtype == X.dtype == Z_new.dtype == torch.float32):
+            raise TypeError(f"{name}: float32 tables only")
+        if not (Z_old.dtype == X.dtype == Z_new.dtype):
+            raise ValueError(f"{name}: Z_old, X, Z_new must share a dtype")
+        return zo, ldz, xp, ldx, zn, ldo
+
+    @staticmethod
+    def _item_blocks(name: str, items_per_block: int, item_e0, *per_item) -> int:
+        """The item blocks of a class pass whose arrays hold `items_per_block` items per block."""
+        n_items = item_e0.numel()
+        if n_items % items_per_block or any(t.numel() != n_items for t in per_item):
+            raise ValueError(f"{name}: the item arrays must hold whole blocks of items_per_block items")
+        return n_items // items_per_block
+
+    @staticmethod
+    def _spmm_flags(sinks_untouched: bool = False, beyond_cache: bool = False, loads: int = 0, ahead: bool = False) -> int:
+        """The flag word of a K3 call (CLANE_SPMM_*; the owned pass: CLANE_OWNED_LOADS(n), CLANE_OWNED_EPILOGUE_AHEAD)."""
+        return ((SPMM_SINKS_UNTOUCHED if sinks_untouched else 0) | (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0)
+                | ((int(loads) & 0xff) << 8) | (OWNED_EPILOGUE_AHEAD if ahead else 0))
+
+    @staticmethod
+    def _owned_plan_fits(name: str, plan: OwnedPlan, width: int, colidx, P, row0: int, Z_old, X, Z_new, partials=None):
+        """The sums of a batch fit the LDS at rows of `width` columns, and the plan stays inside what the call is given
+        (`partials`: where the caller has not checked them tile by tile)."""
+        lanes = 32 if width <= 128 else 64
+        if plan.max_batch_vrows * lanes * 16 > OWNED_LDS_LIMIT:
+            raise ValueError(f"{name}: {plan.max_batch_vrows} virtual rows per batch do not fit the LDS")
+        if (plan.max_edge > min(colidx.numel(), P.numel()) or plan.max_row >= min(X.shape[0], Z_new.shape[0])
+                or row0 + plan.max_row >= Z_old.shape[0] or (partials is not None and plan.max_part >= partials.numel())):
+            raise ValueError(f"{name}: the plan reaches outside colidx / P, the tables or the partials")
+
     def spmm_update(self, rowptr, colidx, P, nrows: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
                     long_threshold: int, partials, sinks_untouched: bool = False, mirror: Optional[Mirror] = None,
                     beyond_cache: bool = False):
         """Main pass: every row of <= long_threshold edges (0 = all rows).  With `sinks_untouched` rows
         without out-edges are neither read nor written (caller keeps Z_new == Z_old there).  `beyond_cache`: the hint
         CLANE_SPMM_TABLE_BEYOND_CACHE (the table is far beyond the caches; results do not depend on it)."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
-        if not (Z_old.dtype == X.dtype == Z_new.dtype):
-            raise ValueError("spmm_update: Z_old, X, Z_new must share a dtype")
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update", Z_old, X, Z_new)
         self._invoke(self._fn("clane_spmm_update", Z_old.dtype), "clane_spmm_update",
                      _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
                      _vec(P, acc_dtype(Z_old.dtype), "P"), nrows, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
-                     long_threshold, (SPMM_SINKS_UNTOUCHED if sinks_untouched else 0) | (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0),
+                     long_threshold, self._spmm_flags(sinks_untouched, beyond_cache),
                      _mirror_arg(mirror, Z_new.dtype), _vec(partials, torch.float64, "partials"), self._stream(Z_old))
 
     def spmm_update_long(self, rowptr, colidx, P, long_rows, waves_per_row: int, row0: int, Z_old, X, gamma: float,
                          Z_new, d: int, partials, mirror: Optional[Mirror] = None):
         """Row-split pass: one workgroup of `waves_per_row` (4 | 16) waves per listed row; writes
         long_rows.numel() partials."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
-        if not (Z_old.dtype == X.dtype == Z_new.dtype):
-            raise ValueError("spmm_update_long: Z_old, X, Z_new must share a dtype")
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_long", Z_old, X, Z_new)
         self._invoke(self._fn("clane_spmm_update_long", Z_old.dtype), "clane_spmm_update_long",
                      _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
                      _vec(P, acc_dtype(Z_old.dtype), "P"), _vec(long_rows, torch.int32, "long_rows"),
@@ -945,9 +972,7 @@ class HipKernels(KernelBackend):
                           Z_old, X, gamma: float, Z_new, d: int, slab, partials, mirror: Optional[Mirror] = None):
         """Hub rows cut into segments over several workgroups + fixed-order combine; writes split_rows.numel()
         partials."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_split", Z_old, X, Z_new)
         self._invoke(self._fn("clane_spmm_update_split", Z_old.dtype), "clane_spmm_update_split",
                      _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
                      _vec(P, acc_dtype(Z_old.dtype), "P"), _vec(split_rows, torch.int32, "split_rows"),
@@ -964,21 +989,16 @@ class HipKernels(KernelBackend):
                           mirror: Optional[Mirror] = None, beyond_cache: bool = False):
         """XCD-affine pass over the listed long rows (edges sorted by (XCD class of the column, column), cut into items; item
         blocks of class b at block index 8 j + b) + fixed-order combine; writes class_rows.numel() partials."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
-        n_items = item_e0.numel()
-        if n_items % items_per_block or item_len.numel() != n_items or item_slot.numel() != n_items:
-            raise ValueError("spmm_update_class: the item arrays must hold whole blocks of items_per_block items")
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_class", Z_old, X, Z_new)
+        n_blocks = self._item_blocks("spmm_update_class", items_per_block, item_e0, item_len, item_slot)
         self._invoke(self._fn("clane_spmm_update_class", Z_old.dtype), "clane_spmm_update_class",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, acc_dtype(Z_old.dtype), "P"),
                      _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
-                     _vec(item_slot, torch.int32, "item_slot"), n_items // items_per_block, items_per_block,
+                     _vec(item_slot, torch.int32, "item_slot"), n_blocks, items_per_block,
                      _vec(class_rows, torch.int32, "class_rows"), _vec(slot_ptr, torch.int64, "slot_ptr"),
                      class_rows.numel(), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
-                     SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0,
-                     _vec(slab, acc_dtype(Z_old.dtype), "slab"), _mirror_arg(mirror, Z_new.dtype),
-                     _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+                     self._spmm_flags(beyond_cache=beyond_cache), _vec(slab, acc_dtype(Z_old.dtype), "slab"),
+                     _mirror_arg(mirror, Z_new.dtype), _vec(partials, torch.float64, "partials"), self._stream(Z_old))
 
     def has_spmm_owned(self, dtype, d: int) -> bool:
         return dtype == torch.float32 and 64 < d <= 256        # 16-byte packs at 32 or 64 lanes per row
@@ -991,22 +1011,12 @@ class HipKernels(KernelBackend):
         """Class rows summed in LDS by row-owning workgroups (no slab, no combine); writes partials[row_part[j]].
         `loads`: CLANE_OWNED_LOADS, row loads in flight per wave (0 = the chunk kernel's choice); `ahead`:
         CLANE_OWNED_EPILOGUE_AHEAD."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
-        if not (Z_old.dtype == X.dtype == Z_new.dtype == torch.float32):
-            raise TypeError("spmm_update_owned: float32 tables only")
-        lanes = 32 if d <= 128 else 64
-        if plan.max_batch_vrows * lanes * 16 > OWNED_LDS_LIMIT:
-            raise ValueError(f"spmm_update_owned: {plan.max_batch_vrows} virtual rows per batch do not fit the LDS")
-        if (plan.max_edge > min(colidx.numel(), P.numel()) or plan.max_row >= min(X.shape[0], Z_new.shape[0])
-                or row0 + plan.max_row >= Z_old.shape[0] or plan.max_part >= partials.numel()):
-            raise ValueError("spmm_update_owned: the plan reaches outside colidx / P, the tables or the partials")
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_owned", Z_old, X, Z_new, f32_only=True)
+        self._owned_plan_fits("spmm_update_owned", plan, d, colidx, P, row0, Z_old, X, Z_new, partials)
         self._invoke(self.lib.clane_spmm_update_owned_f32, "clane_spmm_update_owned",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
                      int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
-                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8)
-                     | (OWNED_EPILOGUE_AHEAD if ahead else 0),
+                     self._spmm_flags(beyond_cache=beyond_cache, loads=loads, ahead=ahead),
                      _vec(partials, torch.float64, "partials"), self._stream(Z_old))
 
     # -- every column tile of a pass in one launch ----------------------------------------------------------
@@ -1020,17 +1030,13 @@ class HipKernels(KernelBackend):
 
     def _tile_args(self, name, Z_old, X, Z_new, d, tile_cols, partials, partials_stride, per_tile):
         """The three whole tables of a fused call and its partials, checked: (zo, ldz, xp, ldx, zn, ldo)."""
-        zo, ldz = _mat(Z_old, "Z_old")
-        xp, ldx = _mat(X, "X")
-        zn, ldo = _mat(Z_new, "Z_new")
-        if not (Z_old.dtype == X.dtype == Z_new.dtype == torch.float32):
-            raise TypeError(f"{name}: float32 tables only")
+        tables = self._tables(name, Z_old, X, Z_new, f32_only=True)
         if not self.has_spmm_tiles(torch.float32, d, tile_cols) or min(Z_old.shape[1], X.shape[1], Z_new.shape[1]) < d:
             raise ValueError(f"{name}: no fused launch for d={d} in tiles of {tile_cols} columns")
         tiles = -(-d // tile_cols)
         if (tiles > 1 and partials_stride < per_tile) or partials.numel() < (tiles - 1) * partials_stride + per_tile:
             raise ValueError(f"{name}: the tiles' partials overlap or end outside `partials`")
-        return zo, ldz, xp, ldx, zn, ldo
+        return tables
 
     def spmm_update_tiles(self, rowptr, colidx, P, nrows: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
                           tile_cols: int, long_threshold: int, partials, partials_stride: int,
@@ -1041,7 +1047,7 @@ class HipKernels(KernelBackend):
         self._invoke(self.lib.clane_spmm_update_tiles_f32, "clane_spmm_update_tiles",
                      _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"),
                      nrows, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols, long_threshold,
-                     (SPMM_SINKS_UNTOUCHED if sinks_untouched else 0) | (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0),
+                     self._spmm_flags(sinks_untouched, beyond_cache),
                      _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
 
     def spmm_update_class_tiles(self, colidx, P, item_e0, item_len, item_slot, items_per_block: int, class_rows, slot_ptr,
@@ -1051,18 +1057,16 @@ class HipKernels(KernelBackend):
         slab[t * spmm_class_slab_len(n_slots, tile_cols):]."""
         zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_class_tiles", Z_old, X, Z_new, d, tile_cols, partials,
                                                     partials_stride, class_rows.numel())
-        n_items = item_e0.numel()
-        if n_items % items_per_block or item_len.numel() != n_items or item_slot.numel() != n_items:
-            raise ValueError("spmm_update_class_tiles: the item arrays must hold whole blocks of items_per_block items")
+        n_blocks = self._item_blocks("spmm_update_class_tiles", items_per_block, item_e0, item_len, item_slot)
         if slab.numel() < -(-d // tile_cols) * self.spmm_class_slab_len(n_slots, tile_cols):
             raise ValueError("spmm_update_class_tiles: the slab does not hold every tile's chunk sums")
         self._invoke(self.lib.clane_spmm_update_class_tiles_f32, "clane_spmm_update_class_tiles",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"),
                      _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
-                     _vec(item_slot, torch.int32, "item_slot"), n_items // items_per_block, items_per_block,
+                     _vec(item_slot, torch.int32, "item_slot"), n_blocks, items_per_block,
                      _vec(class_rows, torch.int32, "class_rows"), _vec(slot_ptr, torch.int64, "slot_ptr"),
                      class_rows.numel(), n_slots, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
-                     SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0, _vec(slab, torch.float32, "slab"),
+                     self._spmm_flags(beyond_cache=beyond_cache), _vec(slab, torch.float32, "slab"),
                      _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
 
     def spmm_update_owned_tiles(self, colidx, P, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X, gamma: float,
@@ -1073,17 +1077,11 @@ class HipKernels(KernelBackend):
                                                     partials_stride, plan.max_part + 1)
         if not self.has_spmm_owned(torch.float32, tile_cols):
             raise ValueError(f"spmm_update_owned_tiles: no owned instance for tiles of {tile_cols} columns")
-        lanes = 32 if tile_cols <= 128 else 64
-        if plan.max_batch_vrows * lanes * 16 > OWNED_LDS_LIMIT:
-            raise ValueError(f"spmm_update_owned_tiles: {plan.max_batch_vrows} virtual rows per batch do not fit the LDS")
-        if (plan.max_edge > min(colidx.numel(), P.numel()) or plan.max_row >= min(X.shape[0], Z_new.shape[0])
-                or row0 + plan.max_row >= Z_old.shape[0]):
-            raise ValueError("spmm_update_owned_tiles: the plan reaches outside colidx / P or the tables")
+        self._owned_plan_fits("spmm_update_owned_tiles", plan, tile_cols, colidx, P, row0, Z_old, X, Z_new)
         self._invoke(self.lib.clane_spmm_update_owned_tiles_f32, "clane_spmm_update_owned_tiles",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
                      int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
-                     (SPMM_TABLE_BEYOND_CACHE if beyond_cache else 0) | ((int(loads) & 0xff) << 8)
-                     | (OWNED_EPILOGUE_AHEAD if ahead else 0),
+                     self._spmm_flags(beyond_cache=beyond_cache, loads=loads, ahead=ahead),
                      _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
 
     def reduce_partials(self, partials, n: int, ws, out):
@@ -1143,16 +1141,14 @@ class HipKernels(KernelBackend):
         np_, ldn = _mat(N, "N")
         if S.dtype != N.dtype:
             raise ValueError("edge_score_class_pair: S and N must share a dtype")
-        n_items = item_e0.numel()
-        if n_items % items_per_block or any(t.numel() != n_items for t in (item_len, item_slot, item_row)):
-            raise ValueError("edge_score_class_pair: the item arrays must hold whole blocks of items_per_block items")
+        n_blocks = self._item_blocks("edge_score_class_pair", items_per_block, item_e0, item_len, item_slot, item_row)
         if fuse_softmax and (stats is None or stats.numel() < 2 * (int(slot_ptr[-1]) if n_slots is None else n_slots)):
             raise ValueError("edge_score_class_pair: stats needs 2 elements per slot")
         self._check(self._fn("clane_edge_score_class_pair", S.dtype)(
             _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
             _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
             _vec(item_slot, torch.int32, "item_slot"), _vec(item_row, torch.int32, "item_row"),
-            n_items // items_per_block, items_per_block, _vec(class_rows, torch.int32, "class_rows"),
+            n_blocks, items_per_block, _vec(class_rows, torch.int32, "class_rows"),
             _vec(slot_ptr, torch.int64, "slot_ptr"), class_rows.numel(), row0, sp, lds, np_, ldn, d,
             _vec(scores, S.dtype, "scores"),
             (SCORE_FUSE_SOFTMAX | ((max(1, min(255, int(row_parts))) & 0xff) << 8)) if fuse_softmax else 0,

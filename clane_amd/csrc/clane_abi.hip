@@ -150,6 +150,38 @@ inline bool mirror_ok(const clane_mirror_t *m, int d) {
     return m == nullptr || m->row_ptr == nullptr || (m->slot != nullptr && m->bufs != nullptr && m->ld >= d);
 }
 
+// The tables of a K3 call: Z_new = f(Z_old, X, gamma) over d columns, copied to the mirror's places where there is one.
+// Every K3 launcher asks its questions of this one place; each reports them under its own name, in its own order.
+template <typename T>
+struct Tables {
+    const T *Z_old;
+    int64_t ldz;
+    const T *X;
+    int64_t ldx;
+    typename Elem<T>::acc_t gamma;
+    T *Z_new;
+    int64_t ldo;
+    int32_t d;
+    const clane_mirror_t *mirror;
+
+    bool mirror_complete() const { return mirror_ok(mirror, d); }
+    bool wide_enough() const { return ldz >= d && ldx >= d && ldo >= d; }
+    bool present() const { return Z_old && X && Z_new; }
+    bool aliased() const { return (const void *)Z_new == (const void *)Z_old; }
+    Mirror<T> mir() const { return make_mirror<T>(mirror); }
+    // the lane layout of a launch over `width` columns a tile (the whole d of a per-tile call)
+    Layout layout(int width) const {
+        return pick_layout<T>(width, {Z_old, X, Z_new, mirror_alignment_probe(mirror, Z_new)},
+                              {ldz, ldx, ldo, mirror && mirror->row_ptr ? mirror->ld : ldo});
+    }
+};
+template <typename T, typename CT, typename GT>
+Tables<T> tables(const CT *Z_old, int64_t ldz, const CT *X, int64_t ldx, GT gamma, CT *Z_new, int64_t ldo, int32_t d,
+                 const clane_mirror_t *mirror = nullptr) {
+    return {reinterpret_cast<const T *>(Z_old), ldz, reinterpret_cast<const T *>(X), ldx, gamma,
+            reinterpret_cast<T *>(Z_new), ldo, d, mirror};
+}
+
 #define REQUIRE(cond, ...) \
     do {                   \
         if (!(cond)) return fail(CLANE_ERR_INVALID_ARGUMENT, __VA_ARGS__); \
@@ -365,82 +397,116 @@ int edge_score_finalize(const int64_t *rowptr, const int32_t *colidx, int64_t nr
 
 inline int64_t spmm_main_grid(int64_t nrows) { return row_grid(nrows); }
 
-template <typename T, typename PT>
-int spmm_update(const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows, int64_t row0,
-                const T *Z_old, int64_t ldz, const T *X, int64_t ldx, typename Elem<T>::acc_t gamma, T *Z_new,
-                int64_t ldo, int32_t d, int64_t long_threshold, int32_t flags, const clane_mirror_t *mirror,
-                double *delta_partials, void *stream) {
-    REQUIRE(nrows >= 0 && row0 >= 0 && d > 0, "spmm_update: bad shape nrows=%lld row0=%lld d=%d", (long long)nrows,
+// Column tiles of a pass: tile t covers columns [t * cols, min(d, (t + 1) * cols)).  Each pass has ONE launcher, and the
+// per-tile call is its one-tile case {d, 0}: the same checks, the same kernel instance (picked by the width of a full
+// tile) and the same grid arithmetic, which is what makes a fused launch bit for bit the per-tile launches.  FUSED, a
+// template parameter that only the three *_tiles_f32 entry points set, decides nothing but which kernel entry receives
+// the arguments: the plain kernel with MIRRORED, or the *_tiles_kernel with a TileGrid (float, 16-byte packs only).
+struct Tiles {
+    int32_t cols;           // columns of every tile but the last, which takes what is left of d
+    int64_t part_stride;    // between the tiles' delta partials
+};
+inline int tile_count(int d, int tile_cols) { return int(ceil_div(d, tile_cols)); }
+// One instance serves all tiles of a fused launch, so the last (narrower) tile must have the lane layout of a full one.
+template <typename T>
+bool tiles_share_layout(int d, int tile_cols) {
+    constexpr int KV = Elem<T>::kVec;
+    auto lanes = [](int w) { const int p = int(ceil_div(w, KV)); return p <= 8 ? 8 : p <= 16 ? 16 : p <= 32 ? 32 : 64; };
+    return tile_cols % KV == 0 && lanes(d - (tile_count(d, tile_cols) - 1) * tile_cols) == lanes(tile_cols);
+}
+#define REQUIRE_TILES(T, d, tiles, what, and_ok, and_text)                                                             \
+    REQUIRE((tiles).cols > 0 && (tiles).cols <= (d) && (and_ok) && tiles_share_layout<T>(d, (tiles).cols),            \
+            "%s: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the lane layout"    \
+            and_text " (d=%d tile_cols=%d)", what, d, (tiles).cols)
+
+// The row pass's kernel entries, per tile and fused: one sub-wave per row for the short rows of narrow matrices
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+constexpr auto row_kernel() {
+    if constexpr (LPR < kWave && VEC > 1) return &spmm_update_subrow_kernel<T, PT, VEC, LPR, U, MIRRORED>;
+    else return &spmm_update_kernel<T, PT, VEC, LPR, U, MIRRORED>;
+}
+template <typename T, typename PT, int VEC, int LPR, int U>
+constexpr auto row_tiles_kernel() {
+    if constexpr (LPR < kWave) return &spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, U>;
+    else return &spmm_update_tiles_kernel<T, PT, VEC, LPR, U>;
+}
+
+template <typename T, typename PT, bool FUSED>
+int spmm_update_impl(const char *what, const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows,
+                     int64_t row0, const Tables<T> &t, Tiles tiles, int64_t long_threshold, int32_t flags,
+                     double *delta_partials, void *stream) {
+    const int32_t d = t.d;
+    REQUIRE(nrows >= 0 && row0 >= 0 && d > 0, "%s: bad shape nrows=%lld row0=%lld d=%d", what, (long long)nrows,
             (long long)row0, d);
-    REQUIRE(mirror_ok(mirror, d), "spmm_update: incomplete mirror descriptor");
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update: leading dimension < d");
-    REQUIRE(long_threshold >= 0, "spmm_update: negative long_threshold");
-    REQUIRE(delta_partials, "spmm_update: null delta_partials");
+    if constexpr (FUSED) REQUIRE_TILES(T, d, tiles, what, true, "");
+    REQUIRE(t.mirror_complete(), "%s: incomplete mirror descriptor", what);
+    REQUIRE(t.wide_enough(), "%s: leading dimension < d", what);
+    REQUIRE(long_threshold >= 0, "%s: negative long_threshold", what);
+    REQUIRE(delta_partials, "%s: null delta_partials", what);
+    const int n_tiles = tile_count(d, tiles.cols);
+    const int per_tile = int(spmm_main_grid(nrows));
+    REQUIRE(tiles.part_stride >= (n_tiles > 1 ? per_tile : 0), "%s: the tiles' partials overlap", what);
+    REQUIRE(int64_t(n_tiles) * per_tile <= INT32_MAX, "%s: grid too large", what);
     if (nrows == 0) return CLANE_OK;
-    REQUIRE(rowptr && colidx && P && Z_old && X && Z_new, "spmm_update: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update: Z_new must not alias Z_old (Jacobi sweep)");
-    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new, mirror_alignment_probe(mirror, Z_new)},
-                                    {ldz, ldx, ldo, mirror && mirror->row_ptr ? mirror->ld : ldo});
-    const int grid = int(spmm_main_grid(nrows));
-    const Mirror<T> mir = make_mirror<T>(mirror);
+    REQUIRE(rowptr && colidx && P && t.present(), "%s: null pointer", what);
+    REQUIRE(!t.aliased(), "%s: Z_new must not alias Z_old (Jacobi sweep)", what);
+    const Layout L = t.layout(tiles.cols);
+    if constexpr (FUSED) REQUIRE(L.vec, "%s: the tables must allow 16-byte packs", what);
+    const unsigned grid = unsigned(n_tiles) * unsigned(per_tile);
+    const bool sinks = (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
+    const Mirror<T> mir = t.mir();
+    const TileGrid tg{per_tile, tiles.cols, tiles.part_stride};
     dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
-        constexpr int U = VEC > 1 ? CLANE_SPMM_U : 4;
-        auto launch = [&]<bool MIRRORED>() {          // the mirrored instances prefetch a row's places (spmm_update.h)
-            if constexpr (LPR == 32 && VEC == 4 && sizeof(T) == 4) {
-                // two fp32 rows per instruction (512-byte rows: the column tiles, config 2, the N = 2 column slices): with the
-                // table far beyond the caches 4 row loads in flight and 8 waves per SIMD beat 8 and 6 (config 3 in two
-                // tiles: row pass 1.58 -> 1.52 ms); a cache-resident table wants the 8 (config 2: 0.103 vs 0.120 ms)
-                if (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) {
-                    spmm_update_subrow_kernel<T, PT, VEC, LPR, CLANE_SUBROW_U32, MIRRORED>
-                        <<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                            rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold,
-                            (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, rows_per_block(nrows), mir,
-                            (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0, delta_partials);
-                    return;
-                }
+        auto launch = [&]<int U>() {
+            auto go = [&](auto *kernel, auto... how) {
+                kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>(rowptr, colidx, P, nrows, row0, t.Z_old, t.ldz, t.X, t.ldx,
+                                                                 t.gamma, t.Z_new, t.ldo, d, long_threshold, sinks,
+                                                                 rows_per_block(nrows), how..., delta_partials);
+            };
+            if constexpr (FUSED) {
+                if constexpr (VEC > 1) go(row_tiles_kernel<T, PT, VEC, LPR, U>(), beyond, tg);
+            } else if (mir.row_ptr != nullptr) {   // the mirrored instances prefetch a row's places (spmm_update.h)
+                go(row_kernel<T, PT, VEC, LPR, U, true>(), mir, beyond);
+            } else {
+                go(row_kernel<T, PT, VEC, LPR, U, false>(), mir, beyond);
             }
-            if constexpr (LPR < kWave && VEC > 1)      // short rows of narrow matrices: one sub-wave per row
-                spmm_update_subrow_kernel<T, PT, VEC, LPR, U, MIRRORED><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold,
-                    (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, rows_per_block(nrows), mir,
-                            (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0, delta_partials);
-            else
-                spmm_update_kernel<T, PT, VEC, LPR, U, MIRRORED><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold,
-                    (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, rows_per_block(nrows), mir,
-                            (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0, delta_partials);
         };
-        if (mir.row_ptr != nullptr) launch.template operator()<true>();
-        else launch.template operator()<false>();
+        // two fp32 rows per instruction (512-byte rows: the column tiles, config 2, the N = 2 column slices): with the
+        // table far beyond the caches 4 row loads in flight and 8 waves per SIMD beat 8 and 6 (config 3 in two
+        // tiles: row pass 1.58 -> 1.52 ms); a cache-resident table wants the 8 (config 2: 0.103 vs 0.120 ms)
+        if constexpr (LPR == 32 && VEC == 4 && sizeof(T) == 4) {
+            if (beyond) return launch.template operator()<CLANE_SUBROW_U32>();
+        }
+        launch.template operator()<(VEC > 1 ? CLANE_SPMM_U : 4)>();
     });
-    return check_launch("spmm_update");
+    return check_launch(what);
 }
 
 template <typename T, typename PT>
 int spmm_update_long(const int64_t *rowptr, const int32_t *colidx, const PT *P, const int32_t *long_rows,
-                     int64_t n_long, int32_t waves_per_row, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                     typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, const clane_mirror_t *mirror,
-                     double *delta_partials, void *stream) {
+                     int64_t n_long, int32_t waves_per_row, int64_t row0, const Tables<T> &t, double *delta_partials,
+                     void *stream) {
+    const int32_t d = t.d;
     REQUIRE(n_long >= 0 && n_long <= INT32_MAX && row0 >= 0 && d > 0, "spmm_update_long: bad shape");
-    REQUIRE(mirror_ok(mirror, d), "spmm_update_long: incomplete mirror descriptor");
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_long: leading dimension < d");
+    REQUIRE(t.mirror_complete(), "spmm_update_long: incomplete mirror descriptor");
+    REQUIRE(t.wide_enough(), "spmm_update_long: leading dimension < d");
     if (n_long == 0) return CLANE_OK;
-    REQUIRE(rowptr && colidx && P && long_rows && Z_old && X && Z_new && delta_partials,
-            "spmm_update_long: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_long: Z_new must not alias Z_old");
-    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new, mirror_alignment_probe(mirror, Z_new)},
-                                    {ldz, ldx, ldo, mirror && mirror->row_ptr ? mirror->ld : ldo});
+    REQUIRE(rowptr && colidx && P && long_rows && t.present() && delta_partials, "spmm_update_long: null pointer");
+    REQUIRE(!t.aliased(), "spmm_update_long: Z_new must not alias Z_old");
+    const Layout L = t.layout(d);
     REQUIRE(waves_per_row == 4 || waves_per_row == 16, "spmm_update_long: waves_per_row must be 4 or 16");
-    const Mirror<T> mir = make_mirror<T>(mirror);
+    const Mirror<T> mir = t.mir();
     dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
         constexpr int U = VEC > 1 ? CLANE_LONG_U : 4;
         if (waves_per_row == 4)
             spmm_long_kernel<T, PT, VEC, LPR, U, 4><<<int(n_long), 4 * kWave, 0, (hipStream_t)stream>>>(
-                rowptr, colidx, P, long_rows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, mir, delta_partials);
+                rowptr, colidx, P, long_rows, row0, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, d, mir,
+                delta_partials);
         else
             spmm_long_kernel<T, PT, VEC, LPR, U, kLongWaves>
                 <<<int(n_long), kLongWaves * kWave, 0, (hipStream_t)stream>>>(
-                    rowptr, colidx, P, long_rows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, mir, delta_partials);
+                    rowptr, colidx, P, long_rows, row0, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, d, mir,
+                    delta_partials);
     });
     return check_launch("spmm_update_long");
 }
@@ -448,80 +514,97 @@ int spmm_update_long(const int64_t *rowptr, const int32_t *colidx, const PT *P, 
 template <typename T, typename PT>
 int spmm_update_split(const int64_t *rowptr, const int32_t *colidx, const PT *P, const int32_t *split_rows,
                       const int64_t *seg_ptr, const int32_t *seg_row, int64_t n_split, int64_t n_segments,
-                      int64_t edges_per_segment, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                      typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d,
-                      typename Elem<T>::acc_t *slab, const clane_mirror_t *mirror, double *delta_partials,
-                      void *stream) {
-    REQUIRE(mirror_ok(mirror, d), "spmm_update_split: incomplete mirror descriptor");
+                      int64_t edges_per_segment, int64_t row0, const Tables<T> &t, typename Elem<T>::acc_t *slab,
+                      double *delta_partials, void *stream) {
+    const int32_t d = t.d;
+    REQUIRE(t.mirror_complete(), "spmm_update_split: incomplete mirror descriptor");
     REQUIRE(n_split >= 0 && n_split <= INT32_MAX && n_segments >= n_split && n_segments <= INT32_MAX && row0 >= 0 &&
                 d > 0 && edges_per_segment >= kWave && edges_per_segment % kWave == 0,
             "spmm_update_split: bad shape (edges_per_segment must be a positive multiple of 64)");
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_split: leading dimension < d");
+    REQUIRE(t.wide_enough(), "spmm_update_split: leading dimension < d");
     if (n_split == 0) return CLANE_OK;
-    REQUIRE(rowptr && colidx && P && split_rows && seg_ptr && seg_row && Z_old && X && Z_new && slab && delta_partials,
+    REQUIRE(rowptr && colidx && P && split_rows && seg_ptr && seg_row && t.present() && slab && delta_partials,
             "spmm_update_split: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_split: Z_new must not alias Z_old");
+    REQUIRE(!t.aliased(), "spmm_update_split: Z_new must not alias Z_old");
     REQUIRE(aligned16(slab), "spmm_update_split: slab must be 16-byte aligned");
-    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new, mirror_alignment_probe(mirror, Z_new)},
-                                    {ldz, ldx, ldo, mirror && mirror->row_ptr ? mirror->ld : ldo});
+    const Layout L = t.layout(d);
     const int64_t ld_slab = ceil_div(d, 8) * 8;
-    const Mirror<T> mir = make_mirror<T>(mirror);
     dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
         constexpr int U = VEC > 1 ? CLANE_LONG_U : 4;
         spmm_split_segment_kernel<T, PT, VEC, LPR, U, kLongWaves>
             <<<unsigned(n_segments), kLongWaves * kWave, 0, (hipStream_t)stream>>>(
-                rowptr, colidx, P, split_rows, seg_ptr, seg_row, edges_per_segment, Z_old, ldz, d, slab, ld_slab);
+                rowptr, colidx, P, split_rows, seg_ptr, seg_row, edges_per_segment, t.Z_old, t.ldz, d, slab, ld_slab);
         // a row's segments sit in the slab like a class row's slots: the same fixed-order combine + epilogue
         spmm_class_combine_kernel<T, VEC, LPR>
             <<<unsigned(ceil_div(n_split, kWave / LPR)), kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
-            split_rows, seg_ptr, n_split, row0, slab, ld_slab, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, mir, false, delta_partials);
+                split_rows, seg_ptr, n_split, row0, slab, ld_slab, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, d,
+                t.mir(), false, delta_partials);
     });
     return check_launch("spmm_update_split");
 }
 
-template <typename T, typename PT>
-int spmm_update_class(const int32_t *colidx, const PT *P, const int64_t *item_e0, const int32_t *item_len,
-                      const int32_t *item_slot, int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
-                      const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const T *Z_old, int64_t ldz, const T *X,
-                      int64_t ldx, typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t flags,
-                      typename Elem<T>::acc_t *slab, const clane_mirror_t *mirror, double *delta_partials,
-                      void *stream) {
-    REQUIRE(mirror_ok(mirror, d), "spmm_update_class: incomplete mirror descriptor");
-    REQUIRE(n_blocks >= 0 && n_blocks <= INT32_MAX && n_rows >= 0 && n_rows <= INT32_MAX && row0 >= 0 && d > 0,
-            "spmm_update_class: bad shape");
+// The class pass over column tiles: chunk sums into the slab (tile t's at slab + t * n_slots * ld_slab, all tiles' at
+// the same time), then the fixed-order combine + epilogue.  The per-tile call has no use for n_slots and passes 0.
+template <typename T, typename PT, bool FUSED>
+int spmm_update_class_impl(const char *what, const int32_t *colidx, const PT *P, const int64_t *item_e0,
+                           const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks, int32_t items_per_block,
+                           const int32_t *class_rows, const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots,
+                           int64_t row0, const Tables<T> &t, Tiles tiles, int32_t flags,
+                           typename Elem<T>::acc_t *slab, double *delta_partials, void *stream) {
+    const int32_t d = t.d;
+    constexpr int kPad = FUSED ? 8 : 1;      // fused: block 8 j + b of every tile on XCD class b, so the count is rounded up
+    REQUIRE(t.mirror_complete(), "%s: incomplete mirror descriptor", what);
+    REQUIRE(n_blocks >= 0 && n_blocks <= INT32_MAX - (FUSED ? 8 : 0) && n_rows >= 0 && n_rows <= INT32_MAX &&
+                n_slots >= 0 && row0 >= 0 && d > 0, "%s: bad shape", what);
+    if constexpr (FUSED) REQUIRE_TILES(T, d, tiles, what, true, "");
     REQUIRE(items_per_block >= kWavesPerBlock && items_per_block <= kMaxItemsPerBlock,
-            "spmm_update_class: items_per_block must be in [%d, %d]", kWavesPerBlock, kMaxItemsPerBlock);
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_class: leading dimension < d");
+            "%s: items_per_block must be in [%d, %d]", what, kWavesPerBlock, kMaxItemsPerBlock);
+    REQUIRE(t.wide_enough(), "%s: leading dimension < d", what);
+    const int n_tiles = tile_count(d, tiles.cols);
+    REQUIRE(tiles.part_stride >= (n_tiles > 1 ? n_rows : 0), "%s: the tiles' partials overlap", what);
     if (n_rows == 0) return CLANE_OK;
-    REQUIRE(colidx && P && item_e0 && item_len && item_slot && class_rows && slot_ptr && Z_old && X && Z_new && slab &&
-                delta_partials,
-            "spmm_update_class: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_class: Z_new must not alias Z_old");
-    REQUIRE(aligned16(slab), "spmm_update_class: slab must be 16-byte aligned");
-    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new, mirror_alignment_probe(mirror, Z_new)},
-                                    {ldz, ldx, ldo, mirror && mirror->row_ptr ? mirror->ld : ldo});
-    const int64_t ld_slab = ceil_div(d, 8) * 8;
-    const Mirror<T> mir = make_mirror<T>(mirror);
+    REQUIRE(colidx && P && item_e0 && item_len && item_slot && class_rows && slot_ptr && t.present() && slab &&
+                delta_partials, "%s: null pointer", what);
+    REQUIRE(!t.aliased(), "%s: Z_new must not alias Z_old", what);
+    REQUIRE(aligned16(slab), "%s: slab must be 16-byte aligned", what);
+    const Layout L = t.layout(tiles.cols);
+    if constexpr (FUSED) REQUIRE(L.vec, "%s: the tables must allow 16-byte packs", what);
+    const int64_t ld_slab = ceil_div(tiles.cols, 8) * 8;
+    const int64_t slab_stride = n_slots * ld_slab;         // clane_spmm_class_slab_len(n_slots, tile_cols) per tile
+    const int chunk_blocks = int(ceil_div(n_blocks, kPad) * kPad);
+    const bool beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
+    REQUIRE(int64_t(n_tiles) * chunk_blocks <= INT32_MAX, "%s: grid too large", what);
     dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
         constexpr int U = VEC > 1 ? CLANE_LONG_U : 4;
         // CLANE_SPMM_TABLE_BEYOND_CACHE: fewer row loads in flight, more waves -- where it was measured to pay (see
-        // spmm_update): two fp32 rows per instruction (6: config 3 in tiles), four bf16 rows (4: config 4's class pass
-        // 2.48 -> 2.36 ms, 98 -> 74 registers)
+        // spmm_update_impl): two fp32 rows per instruction (6: config 3 in tiles), four bf16 rows (4: config 4's class
+        // pass 2.48 -> 2.36 ms, 98 -> 74 registers)
         constexpr int kDeepU = (LPR == 32 && VEC == 4 && sizeof(T) == 4) ? CLANE_CLASS_U32
                                : (LPR == 16 && VEC == 8 && sizeof(T) == 2) ? CLANE_CLASS_U16B : 0;
-        if (n_blocks > 0 && kDeepU > 0 && (flags & CLANE_SPMM_TABLE_BEYOND_CACHE))
-            spmm_class_chunk_kernel<T, PT, VEC, LPR, (kDeepU > 0 ? kDeepU : U)>
-                <<<unsigned(n_blocks), kBlock, 0, (hipStream_t)stream>>>(
-                    colidx, P, item_e0, item_len, item_slot, items_per_block, Z_old, ldz, d, slab, ld_slab);
-        else if (n_blocks > 0)
-            spmm_class_chunk_kernel<T, PT, VEC, LPR, U><<<unsigned(n_blocks), kBlock, 0, (hipStream_t)stream>>>(
-                colidx, P, item_e0, item_len, item_slot, items_per_block, Z_old, ldz, d, slab, ld_slab);
-        spmm_class_combine_kernel<T, VEC, LPR>
-            <<<unsigned(ceil_div(n_rows, kWave / LPR)), kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
-            class_rows, slot_ptr, n_rows, row0, slab, ld_slab, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, mir,
-            (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0, delta_partials);
+        const unsigned chunk_grid = unsigned(n_tiles) * unsigned(chunk_blocks);
+        const int combine_blocks = int(ceil_div(n_rows, kWave / LPR));
+        const unsigned combine_grid = unsigned(n_tiles) * unsigned(combine_blocks);
+        auto chunks = [&]<int CU>() {
+            if constexpr (!FUSED)
+                spmm_class_chunk_kernel<T, PT, VEC, LPR, CU><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
+                    colidx, P, item_e0, item_len, item_slot, items_per_block, t.Z_old, t.ldz, d, slab, ld_slab);
+            else if constexpr (VEC > 1)
+                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, CU><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
+                    colidx, P, item_e0, item_len, item_slot, int(n_blocks), items_per_block, t.Z_old, t.ldz, d, slab,
+                    ld_slab, slab_stride, TileGrid{chunk_blocks, tiles.cols, 0});
+        };
+        if (n_blocks > 0 && kDeepU > 0 && beyond) chunks.template operator()<(kDeepU > 0 ? kDeepU : U)>();
+        else if (n_blocks > 0) chunks.template operator()<U>();
+        if constexpr (!FUSED)
+            spmm_class_combine_kernel<T, VEC, LPR><<<combine_grid, kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
+                class_rows, slot_ptr, n_rows, row0, slab, ld_slab, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, d,
+                t.mir(), beyond, delta_partials);
+        else if constexpr (VEC > 1)
+            spmm_class_combine_tiles_kernel<T, VEC, LPR><<<combine_grid, kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
+                class_rows, slot_ptr, n_rows, row0, slab, ld_slab, slab_stride, t.Z_old, t.ldz, t.X, t.ldx, t.gamma,
+                t.Z_new, t.ldo, d, beyond, TileGrid{combine_blocks, tiles.cols, tiles.part_stride}, delta_partials);
     });
-    return check_launch("spmm_update_class");
+    return check_launch(what);
 }
 
 // LDS of spmm_owned_kernel beyond its sums (the step counters), rounded up generously
@@ -529,54 +612,15 @@ constexpr int64_t kOwnedLdsReserve = 1024;
 constexpr int64_t kLdsPerCU = 160 * 1024;
 constexpr int64_t kLdsDefaultLimit = 64 * 1024;
 
-// Column tiles of one launch: tile t covers columns [t * tile_cols, min(d, (t + 1) * tile_cols)).  The fused calls pick
-// ONE kernel instance for all tiles, by the width of a full tile, so the last (narrower) tile must be one the per-tile
-// call would give the same lane layout: the callers REQUIRE tiles_share_layout.
-inline int tile_count(int d, int tile_cols) { return int(ceil_div(d, tile_cols)); }
-template <typename T>
-bool tiles_share_layout(int d, int tile_cols) {
-    constexpr int KV = Elem<T>::kVec;
-    auto lanes = [](int w) { const int p = int(ceil_div(w, KV)); return p <= 8 ? 8 : p <= 16 ? 16 : p <= 32 ? 32 : 64; };
-    return tile_cols % KV == 0 && lanes(d - (tile_count(d, tile_cols) - 1) * tile_cols) == lanes(tile_cols);
-}
-
-// spmm_update_owned over `n_tiles` column tiles of a table d_all wide (the per-tile call: one tile of d_all columns)
+// The owned class pass over the column tiles of a table t.d wide.  Its kernel has one entry for both forms, so there is
+// no FUSED here; everything but the tiles themselves is reported as spmm_update_owned, whichever entry point was called.
 template <typename T, typename PT>
 int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan,
-                           int32_t block_threads, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                           typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d_all, int32_t tile_cols,
-                           int64_t part_stride, int32_t flags, double *delta_partials, void *stream);
-
-template <typename T, typename PT>
-int spmm_update_owned(const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan, int32_t block_threads,
-                      int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                      typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t flags,
-                      double *delta_partials, void *stream) {
-    return spmm_update_owned_impl<T, PT>("spmm_update_owned", colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx,
-                                         gamma, Z_new, ldo, d, d, 0, flags, delta_partials, stream);
-}
-
-template <typename T, typename PT>
-int spmm_update_owned_tiles(const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan, int32_t block_threads,
-                            int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                            typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t tile_cols,
-                            int32_t flags, double *delta_partials, int64_t partials_tile_stride, void *stream) {
-    REQUIRE(d > 0 && tile_cols > 0 && tile_cols <= d && partials_tile_stride >= 0 && tiles_share_layout<T>(d, tile_cols),
-            "spmm_update_owned_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the "
-            "lane layout, the partials' stride >= 0 (d=%d tile_cols=%d)", d, tile_cols);
-    return spmm_update_owned_impl<T, PT>("spmm_update_owned_tiles", colidx, P, plan, block_threads, row0, Z_old, ldz, X,
-                                         ldx, gamma, Z_new, ldo, d, tile_cols, partials_tile_stride, flags, delta_partials,
-                                         stream);
-}
-
-template <typename T, typename PT>
-int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan,
-                           int32_t block_threads, int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                           typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d_all, int32_t tile_cols,
-                           int64_t part_stride, int32_t flags, double *delta_partials, void *stream) {
+                           int32_t block_threads, int64_t row0, const Tables<T> &t, Tiles tiles, bool fused, int32_t flags,
+                           double *delta_partials, void *stream) {
     using A = typename Elem<T>::acc_t;
-    const int32_t d = tile_cols;           // what the instance and the LDS sums are sized by: one full tile
-    REQUIRE(d_all >= d, "%s: bad shape", what);
+    const int32_t d = tiles.cols;          // what the instance and the LDS sums are sized by: one full tile
+    if (fused) REQUIRE_TILES(T, t.d, tiles, what, tiles.part_stride >= 0, ", the partials' stride >= 0");
     REQUIRE(plan, "spmm_update_owned: null plan");
     REQUIRE(plan->n_groups >= 0 && row0 >= 0 && d > 0, "spmm_update_owned: bad shape");
     REQUIRE(plan->n_steps >= 1 && plan->n_steps <= kOwnedMaxSteps, "spmm_update_owned: n_steps must be in [1, %d]",
@@ -584,15 +628,15 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
     REQUIRE(plan->chunk >= kWave && plan->chunk % kWave == 0, "spmm_update_owned: chunk must be a positive multiple of 64");
     REQUIRE(block_threads >= kWave && block_threads <= kOwnedMaxBlock && block_threads % kWave == 0,
             "spmm_update_owned: block_threads must be a multiple of 64 in [64, %d]", kOwnedMaxBlock);
-    REQUIRE(ldz >= d_all && ldx >= d_all && ldo >= d_all, "spmm_update_owned: leading dimension < d");
+    REQUIRE(t.wide_enough(), "spmm_update_owned: leading dimension < d");
     REQUIRE(plan->max_batch_vrows >= 0, "spmm_update_owned: negative max_batch_vrows");
     if (plan->n_groups == 0) return CLANE_OK;
     REQUIRE(colidx && P && plan->grp_bat_ptr && plan->bat_vrow_ptr && plan->bat_row_ptr && plan->bat_seg_ptr &&
                 plan->seg_e0 && plan->seg_len && plan->seg_vrow && plan->row_id && plan->row_part && plan->row_vptr &&
-                Z_old && X && Z_new && delta_partials,
+                t.present() && delta_partials,
             "spmm_update_owned: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_owned: Z_new must not alias Z_old");
-    const Layout L = pick_layout<T>(d, {Z_old, X, Z_new}, {ldz, ldx, ldo});
+    REQUIRE(!t.aliased(), "spmm_update_owned: Z_new must not alias Z_old");
+    const Layout L = t.layout(d);
     REQUIRE(L.vec && (L.lpr == 32 || L.lpr == 64) && d <= L.lpr * Elem<T>::kVec,
             "spmm_update_owned: no instance for d=%d with these operands (16-byte packs, 17..64 packs per row)", d);
     const int64_t lds = int64_t(plan->max_batch_vrows) * L.lpr * Elem<T>::kVec * int64_t(sizeof(A));
@@ -619,7 +663,8 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
             }
         }
         kernel<<<unsigned(plan->n_groups), unsigned(block_threads), size_t(lds), (hipStream_t)stream>>>(
-            colidx, P, op, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d_all, tile_cols, part_stride, (flags & CLANE_OWNED_EPILOGUE_AHEAD) != 0, beyond, delta_partials);
+            colidx, P, op, row0, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, t.d, tiles.cols, tiles.part_stride,
+            (flags & CLANE_OWNED_EPILOGUE_AHEAD) != 0, beyond, delta_partials);
     };
     constexpr int KV = Elem<T>::kVec;
     // Row loads in flight per wave.  Asked for through CLANE_OWNED_LOADS(n) (the instances: 6, 8, 12 at two rows per
@@ -638,111 +683,6 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
     }
     if (rc != CLANE_OK) return rc;
     return check_launch(what);
-}
-
-// ---- every column tile of a pass in one launch (csrc/spmm_update.h, spmm_update_tiles_kernel) -----------------------
-template <typename T, typename PT>
-int spmm_update_tiles(const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows, int64_t row0,
-                      const T *Z_old, int64_t ldz, const T *X, int64_t ldx, typename Elem<T>::acc_t gamma, T *Z_new,
-                      int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold, int32_t flags,
-                      double *delta_partials, int64_t partials_tile_stride, void *stream) {
-    REQUIRE(nrows >= 0 && row0 >= 0 && d > 0, "spmm_update_tiles: bad shape nrows=%lld row0=%lld d=%d", (long long)nrows,
-            (long long)row0, d);
-    REQUIRE(tile_cols > 0 && tile_cols <= d && tiles_share_layout<T>(d, tile_cols),
-            "spmm_update_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the lane "
-            "layout (d=%d tile_cols=%d)", d, tile_cols);
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_tiles: leading dimension < d");
-    REQUIRE(long_threshold >= 0, "spmm_update_tiles: negative long_threshold");
-    REQUIRE(delta_partials, "spmm_update_tiles: null delta_partials");
-    const int n_tiles = tile_count(d, tile_cols);
-    const int per_tile = int(spmm_main_grid(nrows));
-    REQUIRE(partials_tile_stride >= (n_tiles > 1 ? per_tile : 0), "spmm_update_tiles: the tiles' partials overlap");
-    REQUIRE(int64_t(n_tiles) * per_tile <= INT32_MAX, "spmm_update_tiles: grid too large");
-    if (nrows == 0) return CLANE_OK;
-    REQUIRE(rowptr && colidx && P && Z_old && X && Z_new, "spmm_update_tiles: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_tiles: Z_new must not alias Z_old (Jacobi sweep)");
-    const Layout L = pick_layout<T>(tile_cols, {Z_old, X, Z_new}, {ldz, ldx, ldo});
-    REQUIRE(L.vec, "spmm_update_tiles: the tables must allow 16-byte packs");
-    const TileGrid tg{per_tile, tile_cols, partials_tile_stride};
-    const unsigned grid = unsigned(n_tiles) * unsigned(per_tile);
-    const bool sinks = (flags & CLANE_SPMM_SINKS_UNTOUCHED) != 0, beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
-    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {      // the instance spmm_update picks for a tile of tile_cols columns
-        if constexpr (VEC > 1) {
-            constexpr int U = CLANE_SPMM_U;
-            if constexpr (LPR == 32 && VEC == 4 && sizeof(T) == 4) {
-                if (beyond) {
-                    spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, CLANE_SUBROW_U32><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                        rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
-                        rows_per_block(nrows), beyond, tg, delta_partials);
-                    return;
-                }
-            }
-            if constexpr (LPR < kWave)
-                spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
-                    rows_per_block(nrows), beyond, tg, delta_partials);
-            else
-                spmm_update_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                    rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d, long_threshold, sinks,
-                    rows_per_block(nrows), beyond, tg, delta_partials);
-        }
-    });
-    return check_launch("spmm_update_tiles");
-}
-
-template <typename T, typename PT>
-int spmm_update_class_tiles(const int32_t *colidx, const PT *P, const int64_t *item_e0, const int32_t *item_len,
-                            const int32_t *item_slot, int64_t n_blocks, int32_t items_per_block,
-                            const int32_t *class_rows, const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots,
-                            int64_t row0, const T *Z_old, int64_t ldz, const T *X, int64_t ldx,
-                            typename Elem<T>::acc_t gamma, T *Z_new, int64_t ldo, int32_t d, int32_t tile_cols,
-                            int32_t flags, typename Elem<T>::acc_t *slab, double *delta_partials,
-                            int64_t partials_tile_stride, void *stream) {
-    REQUIRE(n_blocks >= 0 && n_blocks <= INT32_MAX - 8 && n_rows >= 0 && n_rows <= INT32_MAX && n_slots >= 0 && row0 >= 0 &&
-                d > 0, "spmm_update_class_tiles: bad shape");
-    REQUIRE(tile_cols > 0 && tile_cols <= d && tiles_share_layout<T>(d, tile_cols),
-            "spmm_update_class_tiles: tile_cols must be a multiple of the 16-byte pack in (0, d] whose last tile keeps the "
-            "lane layout (d=%d tile_cols=%d)", d, tile_cols);
-    REQUIRE(items_per_block >= kWavesPerBlock && items_per_block <= kMaxItemsPerBlock,
-            "spmm_update_class_tiles: items_per_block must be in [%d, %d]", kWavesPerBlock, kMaxItemsPerBlock);
-    REQUIRE(ldz >= d && ldx >= d && ldo >= d, "spmm_update_class_tiles: leading dimension < d");
-    const int n_tiles = tile_count(d, tile_cols);
-    REQUIRE(partials_tile_stride >= (n_tiles > 1 ? n_rows : 0), "spmm_update_class_tiles: the tiles' partials overlap");
-    if (n_rows == 0) return CLANE_OK;
-    REQUIRE(colidx && P && item_e0 && item_len && item_slot && class_rows && slot_ptr && Z_old && X && Z_new && slab &&
-                delta_partials, "spmm_update_class_tiles: null pointer");
-    REQUIRE((const void *)Z_new != (const void *)Z_old, "spmm_update_class_tiles: Z_new must not alias Z_old");
-    REQUIRE(aligned16(slab), "spmm_update_class_tiles: slab must be 16-byte aligned");
-    const Layout L = pick_layout<T>(tile_cols, {Z_old, X, Z_new}, {ldz, ldx, ldo});
-    REQUIRE(L.vec, "spmm_update_class_tiles: the tables must allow 16-byte packs");
-    const int64_t ld_slab = ceil_div(tile_cols, 8) * 8;
-    const int64_t slab_stride = n_slots * ld_slab;         // clane_spmm_class_slab_len(n_slots, tile_cols) per tile
-    const int chunk_blocks = int(ceil_div(n_blocks, 8) * 8);                 // block 8 j + b of every tile on XCD class b
-    const bool beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
-    REQUIRE(int64_t(n_tiles) * chunk_blocks <= INT32_MAX, "spmm_update_class_tiles: grid too large");
-    dispatch_layout<T>(L, [&]<int VEC, int LPR>() {
-        if constexpr (VEC > 1) {
-            constexpr int U = CLANE_LONG_U;
-            constexpr int kDeepU = (LPR == 32 && VEC == 4 && sizeof(T) == 4) ? CLANE_CLASS_U32 : 0;
-            const TileGrid cg{chunk_blocks, tile_cols, 0};
-            const unsigned grid = unsigned(n_tiles) * unsigned(chunk_blocks);
-            if (n_blocks > 0 && kDeepU > 0 && beyond)
-                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, (kDeepU > 0 ? kDeepU : U)>
-                    <<<grid, kBlock, 0, (hipStream_t)stream>>>(colidx, P, item_e0, item_len, item_slot, int(n_blocks),
-                                                               items_per_block, Z_old, ldz, d, slab, ld_slab, slab_stride, cg);
-            else if (n_blocks > 0)
-                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, U><<<grid, kBlock, 0, (hipStream_t)stream>>>(
-                    colidx, P, item_e0, item_len, item_slot, int(n_blocks), items_per_block, Z_old, ldz, d, slab, ld_slab,
-                    slab_stride, cg);
-            const int combine_blocks = int(ceil_div(n_rows, kWave / LPR));
-            const TileGrid bg{combine_blocks, tile_cols, partials_tile_stride};
-            spmm_class_combine_tiles_kernel<T, VEC, LPR>
-                <<<unsigned(n_tiles) * unsigned(combine_blocks), kCombineWaves * kWave, 0, (hipStream_t)stream>>>(
-                    class_rows, slot_ptr, n_rows, row0, slab, ld_slab, slab_stride, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d,
-                    beyond, bg, delta_partials);
-        }
-    });
-    return check_launch("spmm_update_class_tiles");
 }
 
 template <typename T>
@@ -1589,24 +1529,24 @@ int clane_segment_softmax_f64(const int64_t *rowptr, int64_t nrows, double *vals
     return segment_softmax<double>(rowptr, nrows, vals, min_degree, max_degree, long_rows, n_long, stream);
 }
 
+// K3: a per-tile call is its pass's launcher on one tile of d columns; TABLES packs what every K3 call spells the same way
+#define TABLES(T, ...) tables<T>(Z_old, ldz, X, ldx, gamma, Z_new, ldo, d __VA_OPT__(, ) __VA_ARGS__)
 #define CLANE_SPMM_WRAPPERS(SUF, CT, T, PT, GT)                                                                        \
     int clane_spmm_update_##SUF(const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows,             \
                                 int64_t row0, const CT *Z_old, int64_t ldz, const CT *X, int64_t ldx, GT gamma,       \
                                 CT *Z_new, int64_t ldo, int32_t d, int64_t long_threshold, int32_t flags,             \
                                 const clane_mirror_t *mirror, double *delta_partials, void *stream) {                \
-        return spmm_update<T, PT>(rowptr, colidx, P, nrows, row0, reinterpret_cast<const T *>(Z_old), ldz,            \
-                                  reinterpret_cast<const T *>(X), ldx, gamma, reinterpret_cast<T *>(Z_new), ldo, d,   \
-                                  long_threshold, flags, mirror, delta_partials, stream);                             \
+        return spmm_update_impl<T, PT, false>("spmm_update", rowptr, colidx, P, nrows, row0, TABLES(T, mirror),       \
+                                              Tiles{d, 0}, long_threshold, flags, delta_partials, stream);            \
     }                                                                                                                 \
     int clane_spmm_update_long_##SUF(const int64_t *rowptr, const int32_t *colidx, const PT *P,                       \
-                                     const int32_t *long_rows, int64_t n_long, int32_t waves_per_row, int64_t row0, const CT *Z_old,         \
-                                     int64_t ldz, const CT *X, int64_t ldx, GT gamma, CT *Z_new, int64_t ldo,         \
-                                     int32_t d, const clane_mirror_t *mirror, double *delta_partials, void *stream) { \
-        return spmm_update_long<T, PT>(rowptr, colidx, P, long_rows, n_long, waves_per_row, row0,                     \
-                                       reinterpret_cast<const T *>(Z_old), ldz, reinterpret_cast<const T *>(X), ldx,  \
-                                       gamma, reinterpret_cast<T *>(Z_new), ldo, d, mirror, delta_partials, stream);  \
-    }
-#define CLANE_SPLIT_WRAPPER(SUF, CT, T, PT, GT)                                                                         \
+                                     const int32_t *long_rows, int64_t n_long, int32_t waves_per_row, int64_t row0,   \
+                                     const CT *Z_old, int64_t ldz, const CT *X, int64_t ldx, GT gamma, CT *Z_new,     \
+                                     int64_t ldo, int32_t d, const clane_mirror_t *mirror, double *delta_partials,    \
+                                     void *stream) {                                                                  \
+        return spmm_update_long<T, PT>(rowptr, colidx, P, long_rows, n_long, waves_per_row, row0, TABLES(T, mirror),  \
+                                       delta_partials, stream);                                                       \
+    }                                                                                                                 \
     int clane_spmm_update_split_##SUF(const int64_t *rowptr, const int32_t *colidx, const PT *P,                      \
                                       const int32_t *split_rows, const int64_t *seg_ptr, const int32_t *seg_row,      \
                                       int64_t n_split, int64_t n_segments, int64_t edges_per_segment, int64_t row0,   \
@@ -1614,43 +1554,34 @@ int clane_segment_softmax_f64(const int64_t *rowptr, int64_t nrows, double *vals
                                       int64_t ldo, int32_t d, GT *slab, const clane_mirror_t *mirror,                 \
                                       double *delta_partials, void *stream) {                                         \
         return spmm_update_split<T, PT>(rowptr, colidx, P, split_rows, seg_ptr, seg_row, n_split, n_segments,         \
-                                        edges_per_segment, row0, reinterpret_cast<const T *>(Z_old), ldz,             \
-                                        reinterpret_cast<const T *>(X), ldx, gamma, reinterpret_cast<T *>(Z_new),     \
-                                        ldo, d, slab, mirror, delta_partials, stream);                                \
-    }
-CLANE_SPLIT_WRAPPER(f32, float, float, float, float)
-CLANE_SPLIT_WRAPPER(f64, double, double, double, double)
-CLANE_SPLIT_WRAPPER(bf16, uint16_t, bf16_t, float, float)
-#undef CLANE_SPLIT_WRAPPER
-#define CLANE_CLASS_WRAPPER(SUF, CT, T, PT, GT)                                                                        \
+                                        edges_per_segment, row0, TABLES(T, mirror), slab, delta_partials, stream);    \
+    }                                                                                                                 \
     int clane_spmm_update_class_##SUF(const int32_t *colidx, const PT *P, const int64_t *item_e0,                     \
                                       const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks,            \
                                       int32_t items_per_block, const int32_t *class_rows, const int64_t *slot_ptr,    \
                                       int64_t n_rows, int64_t row0, const CT *Z_old, int64_t ldz, const CT *X,        \
                                       int64_t ldx, GT gamma, CT *Z_new, int64_t ldo, int32_t d, int32_t flags,        \
                                       GT *slab, const clane_mirror_t *mirror, double *delta_partials, void *stream) { \
-        return spmm_update_class<T, PT>(colidx, P, item_e0, item_len, item_slot, n_blocks, items_per_block,           \
-                                        class_rows, slot_ptr, n_rows, row0, reinterpret_cast<const T *>(Z_old), ldz,  \
-                                        reinterpret_cast<const T *>(X), ldx, gamma, reinterpret_cast<T *>(Z_new),     \
-                                        ldo, d, flags, slab, mirror, delta_partials, stream);                         \
+        return spmm_update_class_impl<T, PT, false>("spmm_update_class", colidx, P, item_e0, item_len, item_slot,     \
+                                                    n_blocks, items_per_block, class_rows, slot_ptr, n_rows, 0, row0, \
+                                                    TABLES(T, mirror), Tiles{d, 0}, flags, slab, delta_partials,      \
+                                                    stream);                                                          \
     }
-CLANE_CLASS_WRAPPER(f32, float, float, float, float)
-CLANE_CLASS_WRAPPER(f64, double, double, double, double)
-CLANE_CLASS_WRAPPER(bf16, uint16_t, bf16_t, float, float)
-#undef CLANE_CLASS_WRAPPER
 int clane_spmm_update_owned_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
                                 int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz, const float *X,
                                 int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d, int32_t flags,
                                 double *delta_partials, void *stream) {
-    return spmm_update_owned<float, float>(colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo,
-                                           d, flags, delta_partials, stream);
+    return spmm_update_owned_impl<float, float>("spmm_update_owned", colidx, P, plan, block_threads, row0, TABLES(float),
+                                                Tiles{d, 0}, false, flags, delta_partials, stream);
 }
+// ---- every column tile of a pass in one launch (csrc/spmm_update.h, spmm_update_tiles_kernel): float only ----------
 int clane_spmm_update_tiles_f32(const int64_t *rowptr, const int32_t *colidx, const float *P, int64_t nrows, int64_t row0,
                                 const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new,
                                 int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold, int32_t flags,
                                 double *delta_partials, int64_t partials_tile_stride, void *stream) {
-    return spmm_update_tiles<float, float>(rowptr, colidx, P, nrows, row0, Z_old, ldz, X, ldx, gamma, Z_new, ldo, d,
-                                           tile_cols, long_threshold, flags, delta_partials, partials_tile_stride, stream);
+    return spmm_update_impl<float, float, true>("spmm_update_tiles", rowptr, colidx, P, nrows, row0, TABLES(float),
+                                                Tiles{tile_cols, partials_tile_stride}, long_threshold, flags,
+                                                delta_partials, stream);
 }
 int clane_spmm_update_class_tiles_f32(const int32_t *colidx, const float *P, const int64_t *item_e0,
                                       const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks,
@@ -1659,18 +1590,19 @@ int clane_spmm_update_class_tiles_f32(const int32_t *colidx, const float *P, con
                                       const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
                                       int32_t tile_cols, int32_t flags, float *slab, double *delta_partials,
                                       int64_t partials_tile_stride, void *stream) {
-    return spmm_update_class_tiles<float, float>(colidx, P, item_e0, item_len, item_slot, n_blocks, items_per_block,
-                                                 class_rows, slot_ptr, n_rows, n_slots, row0, Z_old, ldz, X, ldx, gamma,
-                                                 Z_new, ldo, d, tile_cols, flags, slab, delta_partials,
-                                                 partials_tile_stride, stream);
+    return spmm_update_class_impl<float, float, true>("spmm_update_class_tiles", colidx, P, item_e0, item_len, item_slot,
+                                                      n_blocks, items_per_block, class_rows, slot_ptr, n_rows, n_slots,
+                                                      row0, TABLES(float), Tiles{tile_cols, partials_tile_stride}, flags,
+                                                      slab, delta_partials, stream);
 }
 int clane_spmm_update_owned_tiles_f32(const int32_t *colidx, const float *P, const clane_owned_plan_t *plan,
                                       int32_t block_threads, int64_t row0, const float *Z_old, int64_t ldz,
                                       const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
                                       int32_t tile_cols, int32_t flags, double *delta_partials,
                                       int64_t partials_tile_stride, void *stream) {
-    return spmm_update_owned_tiles<float, float>(colidx, P, plan, block_threads, row0, Z_old, ldz, X, ldx, gamma, Z_new,
-                                                 ldo, d, tile_cols, flags, delta_partials, partials_tile_stride, stream);
+    return spmm_update_owned_impl<float, float>("spmm_update_owned_tiles", colidx, P, plan, block_threads, row0,
+                                                TABLES(float), Tiles{tile_cols, partials_tile_stride}, true, flags,
+                                                delta_partials, stream);
 }
 int64_t clane_spmm_class_slab_len(int64_t n_slots, int32_t d) { return n_slots * (ceil_div(d, 8) * 8); }
 int64_t clane_spmm_split_slab_len(int64_t n_segments, int32_t d) { return n_segments * (ceil_div(d, 8) * 8); }
@@ -1679,6 +1611,7 @@ CLANE_SPMM_WRAPPERS(f32, float, float, float, float)
 CLANE_SPMM_WRAPPERS(f64, double, double, double, double)
 CLANE_SPMM_WRAPPERS(bf16, uint16_t, bf16_t, float, float)
 #undef CLANE_SPMM_WRAPPERS
+#undef TABLES
 
 int clane_reduce_partials(const double *partials, int64_t n, double *ws, double *out, void *stream) {
     if (n < 0 || !out || !ws || (n > 0 && !partials))

@@ -859,65 +859,53 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                     continue
                 # one launch per kernel and COLUMN TILE (one tile unless column_tiles > 1): views of the same tables
                 T = len(self.tiles)
-                cut = (lambda M, t: M) if T == 1 else (lambda M, t: M[:, self.tiles[t][0]:self.tiles[t][1]])
-                width = (lambda t: self.d) if T == 1 else (lambda t: self.tiles[t][1] - self.tiles[t][0])
-                # the block's delta partials of tile t from a start of its layout (blocks.PartialLayout) on
-                part = lambda start, t: self.partials[t * partial_off[-1] + po + start:]      # noqa: E731
                 if mir is not None and T > 1:
                     raise AssertionError("column tiles and mirrored launches do not combine")
-
+                cut = (lambda M, t: M) if T == 1 else (lambda M, t: M[:, self.tiles[t][0]:self.tiles[t][1]])
+                cuts = [fused.Tables(cut(Zold, t), cut(Xb, t), cut(Zn, t), self.d if T == 1 else c1 - c0, t)
+                        for t, (c0, c1) in enumerate(self.tiles)]
                 # FUSED passes: one call over the whole tables for all tiles (spmm_update*_tiles); tile t's partials
-                # follow tile 0's at t x the length of a tile's partials, exactly where `part` puts them
+                # follow tile 0's at t x the length of a tile's partials, exactly where the per-tile calls put them
                 on = self.fused_tiles if (T > 1 and mir is None) else frozenset()
-                tile_cols, stride, slab = width(0), partial_off[-1], self.slabs[i % len(self.slabs)]
+                whole = fused.Tables(Zold, Xb, Zn, self.d, 0, (cuts[0].d,), (partial_off[-1],))
+                slab = self.slabs[i % len(self.slabs)]
 
-                def class_launch_tiles(items):      # chunk + combine over `items` for every tile: two launches
-                    return ("call", fused.bind_class(self, items, b.row0, Zold, Xb, gamma, Zn, tile_cols, slab,
-                                                     part(lay.klass, 0), stride))
+                def over_tiles(name, listed, start, bind):
+                    """The calls of one pass over the column tiles, as (whole, per_tile): ([the one call on the whole
+                    tables], T x []) where pass `name` is fused, else ([], [[tile 0's call], [tile 1's], ...]) on cut
+                    views; no calls without `listed` rows.  `bind(v, p)` binds the call on the tables `v`, its delta
+                    partials `p` those of v's tile from `start` of the block's layout (blocks.PartialLayout) on."""
+                    call = lambda v: ("call", bind(v, self.partials[v.tile * partial_off[-1] + po + start:]))  # noqa: E731
+                    if listed is None:
+                        return [], [[]] * T
+                    return ([call(whole)], [[]] * T) if name in on else ([], [[call(v)] for v in cuts])
 
-                def class_launch(items, t):         # chunk + combine over `items` (a ClassItems) of this block
-                    return ("call", self._bind("spmm_update_class", self.colidx, self.P, items.e0, items.len, items.slot,
-                                               items.items_per_block, items.rows, items.slot_ptr, b.row0, cut(Zold, t),
-                                               cut(Xb, t), gamma, cut(Zn, t), width(t), self.slabs[i % len(self.slabs)],
-                                               part(lay.klass, t), mirror=mir, beyond_cache=self.beyond_cache))
-                if rows.owned is not None and "owned" in on:
-                    steps.append(("call", owned.bind_launch_tiles(self, rows.owned.plan, b.row0, Zold, Xb, gamma, Zn,
-                                                                  tile_cols, part(lay.klass, 0), stride)))
-                klass = rows.klass if rows.owned is None else rows.owned.rest
-                if klass is not None and "class" in on:
-                    steps.append(class_launch_tiles(klass))
+                def long_rows(listed, waves, start):            # never fused: the T calls
+                    return sum(over_tiles(None, listed, start, lambda v, p: self._bind(
+                        "spmm_update_long", rp, self.colidx, self.P, listed, waves, b.row0, v.Zold, v.X, gamma, v.Znew, v.d,
+                        p, mirror=mir))[1], [])
+                own, split = rows.owned, rows.split
+                klass = rows.klass if own is None else own.rest
+                own_all, own_t = over_tiles("owned", own, lay.klass, lambda v, p: owned.bind_launch(
+                    self, own.plan, b.row0, v, gamma, p))
+                class_all, class_t = over_tiles("class", klass, lay.klass, lambda v, p: fused.bind_class(
+                    self, klass, b.row0, v, gamma, slab, p, mir))
+                _, split_t = over_tiles(None, split, lay.split, lambda v, p: self._bind(
+                    "spmm_update_split", rp, self.colidx, self.P, split.rows, split.seg_ptr, split.seg_row,
+                    self.segment_edges, b.row0, v.Zold, v.X, gamma, v.Znew, v.d, slab, p, mirror=mir))
+                # the fused calls, then tile by tile: the owned rows in LDS, the rows above them by chunk + combine, the
+                # split rows (the last two through the one slab)
+                steps += own_all + class_all
                 for t in range(T):
-                    if rows.owned is not None and "owned" not in on:   # the owned rows in LDS,
-                        steps.append(("call", owned.bind_launch(self, rows.owned.plan, b.row0, cut(Zold, t), cut(Xb, t),
-                                                                gamma, cut(Zn, t), width(t), part(lay.klass, t))))
-                    if klass is not None and "class" not in on:        # the rows above them by chunk + combine
-                        steps.append(class_launch(klass, t))
-                    if rows.split is not None:
-                        steps.append(("call", self._bind("spmm_update_split", rp, self.colidx, self.P, rows.split.rows,
-                                                         rows.split.seg_ptr, rows.split.seg_row, self.segment_edges, b.row0,
-                                                         cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                         self.slabs[i % len(self.slabs)], part(lay.split, t), mirror=mir)))
+                    steps += own_t[t] + class_t[t] + split_t[t]
                 steps.append(("event", i, 4))
-                for t in range(T):
-                    if rows.hub is not None:
-                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, rows.hub, 16,
-                                                         b.row0, cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                         part(lay.hub, t), mirror=mir)))
+                steps += long_rows(rows.hub, 16, lay.hub)
                 steps.append(("event", i, 1))
-                for t in range(T):
-                    if rows.mid is not None:
-                        steps.append(("call", self._bind("spmm_update_long", rp, self.colidx, self.P, rows.mid, 4,
-                                                         b.row0, cut(Zold, t), cut(Xb, t), gamma, cut(Zn, t), width(t),
-                                                         part(lay.mid, t), mirror=mir)))
+                steps += long_rows(rows.mid, 4, lay.mid)
                 steps.append(("event", i, 2))
-                if "row" in on:
-                    steps.append(("call", fused.bind_row(self, rp, b.nrows, b.row0, Zold, Xb, gamma, Zn, tile_cols,
-                                                         part(lay.main, 0), stride)))
-                for t in range(T if "row" not in on else 0):
-                    steps.append(("call", self._bind("spmm_update", rp, self.colidx, self.P, b.nrows, b.row0, cut(Zold, t),
-                                                     cut(Xb, t), gamma, cut(Zn, t), width(t), self.long_threshold,
-                                                     part(lay.main, t), sinks_untouched=True, mirror=mir,
-                                                     beyond_cache=self.beyond_cache)))
+                row_all, row_t = over_tiles("row", b, lay.main, lambda v, p: fused.bind_row(
+                    self, rp, b.nrows, b.row0, v, gamma, p, mir))
+                steps += sum(row_t, row_all)
                 steps.append(("event", i, 3))
                 if b.span is not None:
                     steps.append(("allgather", Znew[b.span[0]:b.span[1]], Zn))

@@ -1,8 +1,40 @@
-"""The fused column-tile launches of a SweepEngine (csrc/spmm_update.h, the *_tiles_kernel forms): every tile of a pass
-in one launch.  ``has_spmm_tiles`` / ``spmm_update_tiles`` / ``spmm_update_class_tiles`` / ``spmm_update_owned_tiles`` are
-the kernel backend's optional calls (``KernelBackend`` gives them a body that says no): a backend without them keeps one
-launch per tile.  The owned pass's fused launch is owned.bind_launch_tiles."""
+"""The tables one K3 call of a SweepEngine is bound on, and the binders of the passes that have a fused form
+(csrc/spmm_update.h, the *_tiles_kernel forms: every column tile of a pass in one launch).  A call is bound either on one
+tile's cut of the tables or -- fused -- on the whole tables for all tiles; the fused call is the per-tile call under the
+name ``*_tiles``, with `tile_cols` after `d` and the partials' tile stride after the partials, so each pass has ONE
+binder and `Tables` says which form it binds.  ``has_spmm_tiles`` / ``spmm_update_tiles`` / ``spmm_update_class_tiles`` /
+``spmm_update_owned_tiles`` are the kernel backend's optional calls (``KernelBackend`` gives them a body that says no):
+a backend without them keeps one launch per tile.  The owned pass's binder is owned.bind_launch."""
 from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any
+
+
+@dataclass(frozen=True)
+class Tables:
+    """One column tile's views of a block's tables (`tile`: whose partials the call gets); or, fused, the whole tables
+    for all tiles, with `cols` = (tile_cols,) and `strides` = (between the tiles' partials,): what the fused call takes
+    after `d` and after the partials."""
+    Zold: Any
+    X: Any
+    Znew: Any
+    d: int
+    tile: int = 0
+    cols: tuple = ()
+    strides: tuple = ()
+
+    @property
+    def fused(self) -> bool:
+        return bool(self.cols)
+
+    def method(self, per_tile: str) -> str:
+        return per_tile + "_tiles" if self.fused else per_tile
+
+    def mirrored(self, mirror) -> dict:
+        """The `mirror` argument of a per-tile call; the fused calls have none (mirrored engines have no tiles)."""
+        assert not (self.fused and mirror is not None)
+        return {} if self.fused else {"mirror": mirror}
 
 
 def backend_has(eng, tile_cols: int) -> bool:
@@ -10,14 +42,17 @@ def backend_has(eng, tile_cols: int) -> bool:
     return bool(eng.k.has_spmm_tiles(eng.dtype, eng.d, tile_cols))
 
 
-def bind_row(eng, rowptr, nrows: int, row0: int, Zold, Xb, gamma: float, Zn, tile_cols: int, partials, stride: int):
-    """The row pass of one block over ALL column tiles (whole tables; tile t's partials at t x stride)."""
-    return eng._bind("spmm_update_tiles", rowptr, eng.colidx, eng.P, nrows, row0, Zold, Xb, gamma, Zn, eng.d, tile_cols,
-                     eng.long_threshold, partials, stride, sinks_untouched=True, beyond_cache=eng.beyond_cache)
+def bind_row(eng, rowptr, nrows: int, row0: int, v: Tables, gamma: float, partials, mirror=None):
+    """The row pass of one block on `v`."""
+    return eng._bind(v.method("spmm_update"), rowptr, eng.colidx, eng.P, nrows, row0, v.Zold, v.X, gamma, v.Znew, v.d,
+                     *v.cols, eng.long_threshold, partials, *v.strides, sinks_untouched=True, **v.mirrored(mirror),
+                     beyond_cache=eng.beyond_cache)
 
 
-def bind_class(eng, items, row0: int, Zold, Xb, gamma: float, Zn, tile_cols: int, slab, partials, stride: int):
-    """Chunk + combine over `items` (a ClassItems) of one block for ALL column tiles: two launches."""
-    return eng._bind("spmm_update_class_tiles", eng.colidx, eng.P, items.e0, items.len, items.slot, items.items_per_block,
-                     items.rows, items.slot_ptr, int(items.slot_ptr[-1]), row0, Zold, Xb, gamma, Zn, eng.d, tile_cols,
-                     slab, partials, stride, beyond_cache=eng.beyond_cache)
+def bind_class(eng, items, row0: int, v: Tables, gamma: float, slab, partials, mirror=None):
+    """Chunk + combine over `items` (a ClassItems) of one block on `v`: two launches.  The fused call also takes the
+    slots of a tile, whose chunk sums all lie in the slab at the same time."""
+    n_slots = (int(items.slot_ptr[-1]),) if v.fused else ()
+    return eng._bind(v.method("spmm_update_class"), eng.colidx, eng.P, items.e0, items.len, items.slot,
+                     items.items_per_block, items.rows, items.slot_ptr, *n_slots, row0, v.Zold, v.X, gamma, v.Znew, v.d,
+                     *v.cols, slab, partials, *v.strides, **v.mirrored(mirror), beyond_cache=eng.beyond_cache)

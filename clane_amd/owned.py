@@ -46,20 +46,11 @@ def plan_block(eng, layout: PartialLayout, rows_c: np.ndarray, rows_abs: np.ndar
     return OwnedRows(eng.k.make_owned_plan(plan, eng.owned_chunk, dev), rest, n_rest)
 
 
-def bind_launch(eng, plan, row0: int, Zold, Xb, gamma: float, Zn, width: int, partials):
-    """The owned launch of one block and column tile, bound like every other call of a sweep's plan."""
-    return eng._bind("spmm_update_owned", eng.colidx, eng.P, plan, eng.owned_block_threads, row0, Zold, Xb, gamma, Zn,
-                     width, partials, beyond_cache=eng.beyond_cache, loads=eng.owned_loads, **_ahead(eng))
-
-
-def _ahead(eng) -> dict:
-    """`ahead=True` where the engine has the epilogue's look-ahead on -- only backends that declare
-    ``owned_epilogue_ahead`` are ever asked for it."""
-    return {"ahead": True} if getattr(eng, "owned_ahead", False) else {}
-
-
-def bind_launch_tiles(eng, plan, row0: int, Zold, Xb, gamma: float, Zn, tile_cols: int, partials, stride: int):
-    """The owned launch of one block over ALL column tiles (whole tables; tile t's partials at t x stride)."""
-    return eng._bind("spmm_update_owned_tiles", eng.colidx, eng.P, plan, eng.owned_block_threads, row0, Zold, Xb, gamma,
-                     Zn, eng.d, tile_cols, partials, stride, beyond_cache=eng.beyond_cache, loads=eng.owned_loads,
-                     **_ahead(eng))
+def bind_launch(eng, plan, row0: int, v, gamma: float, partials):
+    """The owned launch of one block on `v` (a fused.Tables: one column tile, or all of them in one launch), bound like
+    every other call of a sweep's plan.  `ahead=True` where the engine has the epilogue's look-ahead on -- only backends
+    that declare ``owned_epilogue_ahead`` are ever asked for it."""
+    ahead = {"ahead": True} if getattr(eng, "owned_ahead", False) else {}
+    return eng._bind(v.method("spmm_update_owned"), eng.colidx, eng.P, plan, eng.owned_block_threads, row0, v.Zold, v.X,
+                     gamma, v.Znew, v.d, *v.cols, partials, *v.strides, beyond_cache=eng.beyond_cache,
+                     loads=eng.owned_loads, **ahead)
