@@ -123,6 +123,15 @@ def embedding(args):
         layout_cfg = layout_mod.check_section(hparams["layout"], int(os.environ.get("WORLD_SIZE", "1")))
         layout_labels = layout_mod.resolve_labels(layout_cfg, Path(args.data_root))
 
+    # optional section (extension): label_prediction: {labels: Y | load: label_model.npz, l2: 1.0 | [..], folds: 5, seed: 0,
+    # top: 3, multilabel: false, scope: unlabelled | all} -- a kept classifier on the embeddings the run ends with and its
+    # predictions for the other vertices (classify.py); checked before the graph loads
+    label_pred = None
+    if isinstance(hparams, dict) and "label_prediction" in hparams:
+        from . import classify
+        label_pred = classify.check_section(hparams["label_prediction"], Path(args.data_root),
+                                            int(os.environ.get("WORLD_SIZE", "1")))
+
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
     say('[Embedding]', end='\n')
@@ -292,6 +301,14 @@ def embedding(args):
             io.write("\n")
         say(f"The F1 table of {first['labelled']} labelled vertices is stored in {out.absolute()}.")
 
+    label_model = label_report = None
+    if label_pred is not None:                      # a kept classifier on the embeddings the run ends with
+        from . import classify
+        label_model, label_report = classify.run_section(label_pred, g, args.output_root)
+        classify.write_report(args.output_root, label_report)       # written again below with the arrivals' count
+        say(f"The predicted labels of {label_report['predicted']} vertices ({label_report['model']} model, l2 = "
+            f"{label_report['l2']}) are stored in {args.output_root.joinpath('predicted_labels.tsv').absolute()}.")
+
     if node_clu is not None:                        # k-means on the embeddings the run ends with
         import json
         labels_file = None
@@ -343,6 +360,14 @@ def embedding(args):
                                       new_vertices["max_rounds"], new_vertices["weights"])
         say(f"The embeddings of {report['new_vertices']} new vertices ({report['not_converged']} not converged) are "
             f"stored in {args.output_root.joinpath('Z_new.npy').absolute()}.")
+        if label_model is not None:                 # the same model on the arrivals, in the order of their V
+            from . import classify
+            eng = g.engine()
+            classes, probs = label_model.predict_rows(eng, res.Z.to(eng.device, eng.Zcur.dtype).contiguous(),
+                                                      top=label_pred["top"])
+            label_report["predicted_new"] = classify.write_predictions_tsv(
+                args.output_root.joinpath('predicted_labels_new.tsv'), new_ids, label_model.class_names, classes, probs)
+            classify.write_report(args.output_root, label_report)
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

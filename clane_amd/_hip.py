@@ -117,6 +117,10 @@ for _s in ("f32", "f64", "bf16"):   # node classification probe (csrc/label_prob
     SIGNATURES[f"clane_probe_grad_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p])
     SIGNATURES[f"clane_probe_forward_ovr_{_s}"] = (      # multi-label probe (csrc/multilabel_probe.h)
         C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p])
+    SIGNATURES[f"clane_probe_predict_{_s}"] = (          # applying fitted probes (csrc/label_predict.h)
+        C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p])
+PREDICT_SIGMOID, PREDICT_WRITE_PROBA = 1, 2     # CLANE_PREDICT_*
+PREDICT_MAX_TOP = 8                 # CLANE_PREDICT_MAX_TOP
 SIGNATURES["clane_probe_loss_ws_len"] = (_i64, [_i64, _i32])
 SIGNATURES["clane_probe_grad_ws_len"] = (_i64, [_i64, _i32, _i32])
 for _s in ("f32", "f64", "bf16"):   # node clustering (csrc/kmeans.h)
@@ -574,6 +578,15 @@ class KernelBackend(abc.ABC):
     def probe_grad(self, Z, d: int, rows, G, ws, dW, db):
         """dW [K, d] = G^T . Z[rows, :d], db [K] = the column sums of G."""
         raise NotImplementedError(f"{type(self).__name__} has no probe_grad")
+
+    def probe_predict(self, Z, d: int, rows, W, bias, F: int, C: int, top_class, top_prob, proba=None,
+                      sigmoid: bool = False, col_state=None):
+        """Apply F stacked models to the rows: top_class (int32) / top_prob (accumulate dtype) [n, F, top_m], 1 <= top_m
+        <= 8, the classes of highest value best first (ties to the lowest class, NaN and -inf never, the rest -1 / 0);
+        with ``proba`` [n, F, C] every class's probability.  Soft-max over a fit's C classes with the value the logit, or
+        (``sigmoid``, one-vs-rest models) a sigmoid per column with ``col_state`` int8 [F * Cp]: a column of state -1 /
+        +1 has value -inf / +inf and probability 0 / 1."""
+        raise NotImplementedError(f"{type(self).__name__} has no probe_predict")
 
     # node clustering (cluster.py): optional in the same way -- KMeans is the only caller.  rows / order are TABLE ROWS
     # (int32); centres [R, K, d], csq [R, K], best and the workspace in the accumulate dtype.
@@ -1365,6 +1378,36 @@ class HipKernels(KernelBackend):
         self._invoke(self._fn("clane_probe_grad", Z.dtype), "clane_probe_grad",
                      zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(G, acc, "G"), K,
                      _vec(ws, acc, "ws"), _vec(dW, acc, "dW"), _vec(db, acc, "db"), self._stream(Z))
+
+    def probe_predict(self, Z, d: int, rows, W, bias, F: int, C: int, top_class, top_prob, proba=None,
+                      sigmoid: bool = False, col_state=None):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        K = F * (ovr_padded_classes(C) if sigmoid else probe_padded_classes(C))
+        if Z.shape[1] < d or rows.dim() != 1:
+            raise ValueError(f"probe_predict: Z must have at least d = {d} columns and rows be a vector")
+        if tuple(W.shape) != (K, d) or bias.numel() != K:
+            raise ValueError(f"probe_predict: W must be [F * Cp, d] = [{K}, {d}] and bias [{K}], got {tuple(W.shape)}, "
+                             f"{tuple(bias.shape)}")
+        if sigmoid and (col_state is None or col_state.numel() != K):
+            raise ValueError(f"probe_predict: sigmoid needs col_state [{K}]")
+        if top_class.dim() != 3 or tuple(top_class.shape[:2]) != (n, F) or top_class.dtype != torch.int32 \
+                or not 1 <= top_class.shape[2] <= PREDICT_MAX_TOP or top_prob.shape != top_class.shape:
+            raise ValueError(f"probe_predict: top_class (int32) and top_prob must be [n, F, 1..{PREDICT_MAX_TOP}]")
+        flags = PREDICT_SIGMOID if sigmoid else 0
+        pp = None
+        if proba is not None:
+            if tuple(proba.shape) != (n, F, C):
+                raise ValueError(f"probe_predict: proba must be [n, F, C] = [{n}, {F}, {C}]")
+            flags, pp = flags | PREDICT_WRITE_PROBA, _vec(proba, acc, "proba")
+        if n == 0:
+            return
+        self._invoke(self._fn("clane_probe_predict", Z.dtype), "clane_probe_predict",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(W, acc, "W"),
+                     _vec(bias, acc, "bias"), _vec(col_state, torch.int8, "col_state") if sigmoid else None, F, C,
+                     int(top_class.shape[2]), flags, _vec(top_class, torch.int32, "top_class"),
+                     _vec(top_prob, acc, "top_prob"), pp, self._stream(Z))
 
     # -- node clustering -------------------------------------------------------------------
     def kmeans_update_ws_len(self, n: int, R: int, K: int, d: int) -> int:

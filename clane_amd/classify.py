@@ -22,11 +22,14 @@ as 64-bit masks in int64 tensors (bit c: class c), predictions too.
 """
 from __future__ import annotations
 
+import json
 import math
+import os
 from dataclasses import dataclass
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -225,6 +228,70 @@ def table_and_rows(eng, vertices, table: str = "Z"):
     raise ValueError(f"table must be 'Z' or 'X', got {table!r}")
 
 
+# ---- cross-validation: host side --------------------------------------------------------------------------------
+def fold_assignment(n: int, folds: int, seed: int) -> torch.Tensor:
+    """int64 [n] on the CPU: the fold of every labelled row -- the row at position p of one CPU permutation seeded
+    ``seed`` is in fold p mod folds."""
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+    fold = torch.empty(n, dtype=torch.int64)
+    fold[perm] = torch.arange(n) % int(folds)
+    return fold
+
+
+def choose_l2(table: Sequence[dict]) -> float:
+    """The l2 of the row of lowest ``log_loss``, ties to the larger l2; rows without a used fit (NaN) never."""
+    best = None
+    for row in table:
+        if not row["fits_used"] or math.isnan(row["log_loss"]):
+            continue
+        if best is None or row["log_loss"] < best["log_loss"] or \
+                (row["log_loss"] == best["log_loss"] and row["l2"] > best["l2"]):
+            best = row
+    if best is None:
+        raise ValueError("cross-validation: every fit was skipped (no fold trains on two classes)")
+    return float(best["l2"])
+
+
+def calibration_error(prob: torch.Tensor, correct: torch.Tensor, held: torch.Tensor, bins: int = 10) -> torch.Tensor:
+    """float64 [F]: the expected calibration error per fit over its held-out rows -- ``bins`` equal-width bins of the
+    top-1 probability prob [n, F]; sum over the bins of (rows in the bin / held-out rows) |accuracy - mean probability|."""
+    p = prob.double()
+    b = (p * bins).floor().long().clamp(0, bins - 1)
+    F = p.shape[1]
+    key = (torch.arange(F, device=p.device)[None, :] * bins + b)[held]
+    count = torch.bincount(key, minlength=F * bins).double()
+    conf = torch.bincount(key, weights=p[held], minlength=F * bins)
+    hits = torch.bincount(key, weights=correct.double()[held], minlength=F * bins)
+    gap = (hits - conf).abs().view(F, bins).sum(1)                      # n_b |acc_b - conf_b| = |hits_b - conf sum_b|
+    return gap / count.view(F, bins).sum(1).clamp(min=1.0)
+
+
+@dataclass
+class Prediction:
+    classes: torch.Tensor       # [n, F, top] int32: the classes of highest probability, best first; -1: none left
+    probs: torch.Tensor         # [n, F, top], accumulate dtype: their probabilities; 0 where the class is -1
+    proba: Optional[torch.Tensor] = None        # [n, F, C]: every class's probability, on request
+
+
+@dataclass
+class CrossValidation:
+    rows: List[dict]            # per l2: {l2, log_loss, accuracy | micro_f1, ece (soft-max), fits_used}
+    l2: float                   # the chosen value
+    folds: int
+    seed: int
+    fold: torch.Tensor          # [n] int64, CPU: the fold of every labelled row
+    split: torch.Tensor         # [n, folds * len(grid)] uint8, CPU: fit g * folds + k trains on the rows outside fold k
+    l2_per_fit: torch.Tensor    # [F] float64
+    fit: "ProbeFit"
+    log_loss: torch.Tensor      # [F] float64: held-out, per held-out row
+    score: torch.Tensor         # [F] float64: held-out accuracy / micro-F1
+    ece: Optional[torch.Tensor]
+
+    def table(self) -> dict:
+        """What a LabelModel keeps and the CLI writes."""
+        return {"folds": self.folds, "seed": self.seed, "l2": self.l2, "rows": [dict(r) for r in self.rows]}
+
+
 # ---- the fit ----------------------------------------------------------------------------------------------------
 @dataclass
 class ProbeFit:
@@ -281,9 +348,11 @@ class LabelProbe:
         return [(a, min(a + per, F)) for a in range(0, F, per)]
 
     # ---- the batched fit ----------------------------------------------------------------------------------------
-    def fit(self, Z: torch.Tensor, rows: torch.Tensor, y: torch.Tensor, split: torch.Tensor, C: int) -> ProbeFit:
+    def fit(self, Z: torch.Tensor, rows: torch.Tensor, y: torch.Tensor, split: torch.Tensor, C: int,
+            l2=None) -> ProbeFit:
         """Fit every column of ``split`` (uint8 [n, F]) on the rows ``rows`` (int32 table rows of ``Z``) with classes
-        ``y`` (integers in [0, C))."""
+        ``y`` (integers in [0, C)).  ``l2``: None -- the constructor's value for every fit -- or one value per fit
+        (a sequence or tensor [F])."""
         eng, k = self.eng, self.k
         dev, d = Z.device, eng.d
         acc = _hip.acc_dtype(Z.dtype)
@@ -308,7 +377,7 @@ class LabelProbe:
             k.probe_forward(Z, d, rows, y, split[:, a:b], Wg, bg, b - a, C, loss_ws, loss,
                             G=G, pred=pred[:, a:b] if want_pred else None)
 
-        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward)
+        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward, l2)
         nw = Cp * d
         W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
         b = x[:, nw:][:, :C].to(acc).contiguous()
@@ -316,7 +385,7 @@ class LabelProbe:
                         converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train)
 
     def fit_multilabel(self, Z: torch.Tensor, rows: torch.Tensor, masks: torch.Tensor, split: torch.Tensor, C: int,
-                       predict: str = "top_k") -> ProbeFit:
+                       predict: str = "top_k", l2=None) -> ProbeFit:
         """One-vs-rest: every column of ``split`` fits one binary logistic regression per class on the rows ``rows``,
         whose class sets are ``masks`` (int64 [n], bit c: class c -- ``label_masks``).  The objective is ``J_f`` with the
         sum of the fitted columns' binary cross-entropies in place of the soft-max cross-entropy; it is separable over
@@ -325,7 +394,7 @@ class LabelProbe:
         / always, and counted in ``constant``.  A fit without a fitted column is ``skipped``.  ``pred`` holds int64 masks
         of EVERY row: ``predict="top_k"`` gives a row with k true classes the k classes of highest logit (ties to the
         lowest class; a constant-positive column first, a constant-negative one never), ``"threshold"`` the classes of
-        logit > 0."""
+        logit > 0.  ``l2`` as in ``fit``."""
         if predict not in ("top_k", "threshold"):
             raise ValueError(f"predict must be 'top_k' or 'threshold', got {predict!r}")
         if not 1 <= int(C) <= _hip.PROBE_MAX_CLASSES:
@@ -360,7 +429,7 @@ class LabelProbe:
             k.probe_forward_ovr(Z, d, rows, masks, split[:, a:b], Wg, bg, col_state[a * Cp:b * Cp], b - a, C, max_labels,
                                 loss_ws, loss, G=G, pred=pred[:, a:b] if want_pred else None, top_k=top_k)
 
-        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward)
+        x, J, gmax, iterations = self._minimise(Z, rows, F, Cp, skipped, n_train, forward, l2)
         nw = Cp * d
         W = x[:, :nw].view(F, Cp, d)[:, :C].to(acc).contiguous()
         b = x[:, nw:][:, :C].to(acc).contiguous()
@@ -368,13 +437,22 @@ class LabelProbe:
                         converged=~skipped & (gmax <= self.gtol), skipped=skipped, pred=pred, n_train=n_train,
                         constant=constant)
 
-    def _minimise(self, Z, rows, F: int, Cp: int, skipped, n_train, forward):
+    @staticmethod
+    def per_fit_l2(l2, F: int) -> torch.Tensor:
+        """float64 [F] on the CPU from a sequence or tensor of F values, each >= 0."""
+        t = torch.as_tensor(l2, dtype=torch.float64).detach().cpu().reshape(-1)
+        if t.numel() != F or not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError(f"l2 must hold one finite value >= 0 per fit ({F}), got {t.tolist()}")
+        return t
+
+    def _minimise(self, Z, rows, F: int, Cp: int, skipped, n_train, forward, l2=None):
         """The batched L-BFGS both probes share: (x [F, Cp (d + 1)], J, grad_max, iterations), then one last pass that
         writes the predictions.  ``forward(a, b, Wg, bg, loss_ws, loss, G, want_pred)`` makes the forward kernel call for
         the fits [a, b) of one group: the losses into ``loss`` [b - a], d loss / d logits into ``G`` unless it is None,
-        the predictions where ``want_pred``."""
+        the predictions where ``want_pred``.  ``l2``: None (``self.l2`` for every fit) or one value per fit."""
         eng, k = self.eng, self.k
         dev, d = Z.device, eng.d
+        l2_f = None if l2 is None else self.per_fit_l2(l2, F).to(dev)
         acc = _hip.acc_dtype(Z.dtype)
         n = int(rows.numel())
         groups = self.groups(n, F, Cp, acc)
@@ -408,9 +486,12 @@ class LabelProbe:
                     g[a:b, :nw] = dW[:Kg * d].view(b - a, nw).double()
                     g[a:b, nw:] = db[:Kg].view(b - a, Cp).double()
             Wm = x[:, :nw]
-            J = (loss + 0.5 * self.l2 * (Wm * Wm).sum(1)) / n_f
+            if l2_f is None:
+                J = (loss + 0.5 * self.l2 * (Wm * Wm).sum(1)) / n_f
+            else:
+                J = (loss + (0.5 * l2_f) * (Wm * Wm).sum(1)) / n_f
             if want_grad:
-                g[:, :nw] += self.l2 * Wm
+                g[:, :nw] += self.l2 * Wm if l2_f is None else l2_f[:, None] * Wm
                 g /= n_f[:, None]
             return J, g
 
@@ -496,6 +577,159 @@ class LabelProbe:
         evaluate(x, False, None, want_pred=True)
         return x, J, gmax, iterations
 
+    # ---- applying fitted weights --------------------------------------------------------------------------------
+    @staticmethod
+    def stacked(W: torch.Tensor, b: torch.Tensor, C: int, Cp: int, acc: torch.dtype, dev):
+        """(W_all [F * Cp, d], b_all [F * Cp]) in the kernels' layout from W [F, C, d] (or [C, d]) and b [F, C] (or [C]):
+        fit f's class c in row f * Cp + c, zero rows for the pad classes."""
+        W = W.reshape(-1, C, W.shape[-1]) if W.dim() != 3 else W
+        F, d = int(W.shape[0]), int(W.shape[2])
+        b = b.reshape(F, -1)
+        if W.shape[1] != C or tuple(b.shape) != (F, C):
+            raise ValueError(f"weights must be W [F, C, d] and b [F, C] with C = {C}, got {tuple(W.shape)}, {tuple(b.shape)}")
+        W_all = torch.zeros(F, Cp, d, dtype=acc, device=dev)
+        b_all = torch.zeros(F, Cp, dtype=acc, device=dev)
+        W_all[:, :C] = W.to(dev, acc)
+        b_all[:, :C] = b.to(dev, acc)
+        return W_all.view(F * Cp, d), b_all.view(-1)
+
+    def predict(self, Z: torch.Tensor, rows: torch.Tensor, W: torch.Tensor, b: torch.Tensor, C: int, top: int = 1,
+                proba: bool = False, multilabel: bool = False, col_state=None) -> "Prediction":
+        """Apply F models (W [F, C, d], b [F, C]; one model may come as [C, d], [C]) to the rows ``rows`` (int32 table
+        rows of ``Z``): per (row, model) the ``top`` classes of highest probability, best first, and their probabilities
+        -- soft-max over the C classes, or (``multilabel``) one sigmoid per class with ``col_state`` (int8 [F, C] or [C];
+        None: every column fitted) giving a constant column probability 0 / 1.  Ties go to the lowest class; where fewer
+        than ``top`` classes can be chosen the rest is -1 / 0.  One kernel pass (csrc/label_predict.h)."""
+        top = int(top)
+        if not 1 <= top <= _hip.PREDICT_MAX_TOP:
+            raise ValueError(f"predict: top must be in 1..{_hip.PREDICT_MAX_TOP}, got {top}")
+        dev, acc = Z.device, _hip.acc_dtype(Z.dtype)
+        C = int(C)
+        Cp = _hip.ovr_padded_classes(C) if multilabel else _hip.probe_padded_classes(C)
+        W_all, b_all = self.stacked(W, b, C, Cp, acc, dev)
+        d, F = int(W_all.shape[1]), int(W_all.shape[0]) // Cp
+        if Z.dim() != 2 or Z.shape[1] < d:
+            raise ValueError(f"predict: the table has rows of {tuple(Z.shape)[1:]} elements, the weights need d = {d}")
+        rows = rows.to(dev, torch.int32).contiguous()
+        n = int(rows.numel())
+        state = None
+        if multilabel:
+            state = torch.zeros(F, Cp, dtype=torch.int8, device=dev)
+            if col_state is not None:
+                cs = torch.as_tensor(col_state).to(dev, torch.int8).reshape(-1, C)
+                if cs.shape[0] != F:
+                    raise ValueError(f"predict: col_state must be [F, C] = [{F}, {C}], got {tuple(cs.shape)}")
+                state[:, :C] = cs
+            state = state.view(-1)
+        classes = torch.empty(n, F, top, dtype=torch.int32, device=dev)
+        probs = torch.empty(n, F, top, dtype=acc, device=dev)
+        full = torch.empty(n, F, C, dtype=acc, device=dev) if proba else None
+        self.k.probe_predict(Z, d, rows, W_all, b_all, F, C, classes, probs, proba=full, sigmoid=bool(multilabel),
+                             col_state=state)
+        return Prediction(classes=classes, probs=probs, proba=full)
+
+    # ---- choosing l2 --------------------------------------------------------------------------------------------
+    def cross_validate(self, Z: torch.Tensor, rows: torch.Tensor, y_or_masks: torch.Tensor, C: int, l2_grid,
+                       folds: int = 5, seed: int = 0, multilabel: bool = False) -> "CrossValidation":
+        """``folds``-fold cross-validation of every l2 of ``l2_grid`` on the labelled rows, all ``folds * len(l2_grid)``
+        fits as ONE batched fit (fit g * folds + k: grid value g without fold k).  Folds: one CPU permutation seeded
+        ``seed`` (``make_splits``' generator convention), the row at position p of it in fold p mod folds.  Per fit the
+        held-out log-loss -- the forward kernel on the complement split at the final weights, over the held-out rows --
+        the held-out accuracy (multi-label: micro-F1 of the top-k prediction) and, soft-max only, the expected
+        calibration error over 10 equal-width bins of the held-out top-1 probability.  The chosen l2 has the lowest mean
+        held-out log-loss over the fits that were not skipped, ties to the larger l2."""
+        grid = [float(v) for v in l2_grid]
+        folds, C = int(folds), int(C)
+        n = int(rows.numel())
+        if not grid or any(not (v >= 0 and math.isfinite(v)) for v in grid) or len(set(grid)) != len(grid):
+            raise ValueError(f"cross_validate: l2_grid must hold distinct finite values >= 0, got {list(l2_grid)}")
+        if not 2 <= folds <= n:
+            raise ValueError(f"cross_validate: folds must be in 2..{n} (the labelled rows), got {folds}")
+        dev, acc = Z.device, _hip.acc_dtype(Z.dtype)
+        fold = fold_assignment(n, folds, seed)
+        Fn = folds * len(grid)
+        split = (fold[:, None] != torch.arange(folds)[None, :]).to(torch.uint8).repeat(1, len(grid)).contiguous()
+        l2_f = torch.tensor(grid, dtype=torch.float64).repeat_interleave(folds)
+        rows = rows.to(dev, torch.int32).contiguous()
+        held = (split == 0).to(dev)
+        comp = held.to(torch.uint8).contiguous()
+        n_held = held.sum(0).double()
+        loss = torch.zeros(Fn, dtype=torch.float64, device=dev)
+        loss_ws = torch.empty(self.k.probe_loss_ws_len(n, Fn), dtype=torch.float64, device=dev)
+        ece = None
+        if multilabel:
+            masks = y_or_masks.to(dev).reshape(-1).contiguous()
+            fit = self.fit_multilabel(Z, rows, masks, split, C, predict="top_k", l2=l2_f)
+            Cp = _hip.ovr_padded_classes(C)
+            W_all, b_all = self.stacked(fit.W, fit.b, C, Cp, acc, dev)
+            state = torch.zeros(Fn, Cp, dtype=torch.int8, device=dev)
+            state[:, :C] = column_states(masks, split.to(dev), C)
+            max_labels = int(mask_bits(masks, C).sum(1).max()) if n else 0
+            self.k.probe_forward_ovr(Z, self.eng.d, rows, masks, comp, W_all, b_all, state.view(-1), Fn, C, max_labels,
+                                     loss_ws, loss)
+            score, _ = f1_from_counts(multilabel_counts(masks, fit.pred, held, C))
+        else:
+            y = y_or_masks.to(dev, torch.int32).reshape(-1).contiguous()
+            fit = self.fit(Z, rows, y, split, C, l2=l2_f)
+            Cp = _hip.probe_padded_classes(C)
+            W_all, b_all = self.stacked(fit.W, fit.b, C, Cp, acc, dev)
+            self.k.probe_forward(Z, self.eng.d, rows, y, comp, W_all, b_all, Fn, C, loss_ws, loss)
+            hit = (fit.pred == y[:, None]) & held
+            score = hit.sum(0).double() / n_held.clamp(min=1.0)
+            top1 = self.predict(Z, rows, fit.W, fit.b, C, top=1)
+            ece = calibration_error(top1.probs[:, :, 0], top1.classes[:, :, 0] == y[:, None], held)
+        log_loss = loss / n_held.clamp(min=1.0)
+        used = ~fit.skipped
+        table = []
+        for g, v in enumerate(grid):
+            sl = slice(g * folds, (g + 1) * folds)
+            u = used[sl]
+            m = int(u.sum())
+            mean = lambda t: float(t[sl][u].double().mean()) if m else float("nan")     # noqa: E731
+            row = {"l2": v, "log_loss": mean(log_loss), "micro_f1" if multilabel else "accuracy": mean(score)}
+            if ece is not None:
+                row["ece"] = mean(ece)
+            row["fits_used"] = m
+            table.append(row)
+        return CrossValidation(rows=table, l2=choose_l2(table), folds=folds, seed=int(seed), fold=fold, split=split,
+                               l2_per_fit=l2_f, fit=fit, log_loss=log_loss, score=score, ece=ece)
+
+    def train(self, vertices, y, n_classes: int, l2=1.0, folds: int = 5, seed: int = 0, table: str = "Z",
+              multilabel: bool = False, class_names: Optional[Sequence] = None) -> "LabelModel":
+        """A kept classifier from the labelled vertices (``evaluate``'s forms of ``y``): a list of ``l2`` is chosen among
+        by ``cross_validate``; then ONE fit on all labelled rows at the (chosen) value."""
+        Z, rows = self.table_and_rows(vertices, table)
+        n, C = int(rows.numel()), int(n_classes)
+        if multilabel:
+            y = label_masks(y, C)
+        else:
+            y = torch.as_tensor(y, dtype=torch.int64).reshape(-1)
+        if y.numel() != n:
+            raise ValueError("train: one class (set) per labelled vertex")
+        names = [str(c) for c in range(C)] if class_names is None else [str(c) for c in class_names]
+        if len(names) != C:
+            raise ValueError(f"train: {len(names)} class names for {C} classes")
+        cv = None
+        if isinstance(l2, (list, tuple)) or (isinstance(l2, torch.Tensor) and l2.dim() > 0):
+            cv = self.cross_validate(Z, rows, y, C, l2, folds=folds, seed=seed, multilabel=multilabel)
+            value = cv.l2
+        else:
+            value = float(l2)
+        ones = torch.ones(n, 1, dtype=torch.uint8)
+        if multilabel:
+            fit = self.fit_multilabel(Z, rows, y, ones, C, l2=[value])
+            state = column_states(y.to(Z.device), ones.to(Z.device), C)[0].cpu().numpy()
+        else:
+            fit = self.fit(Z, rows, y, ones, C, l2=[value])
+            state = None
+        if bool(fit.skipped[0]):
+            raise ValueError("train: the labelled vertices hold fewer than 2 classes" if not multilabel else
+                             "train: every class is held by no or by every labelled vertex")
+        return LabelModel(W=fit.W[0].cpu().numpy(), b=fit.b[0].cpu().numpy(), class_names=names,
+                          multilabel=bool(multilabel), l2=value, col_state=state, d=int(fit.W.shape[2]), table=table,
+                          n_train=n, objective=float(fit.objective[0]), iterations=int(fit.iterations[0]),
+                          converged=bool(fit.converged[0]), cv=None if cv is None else cv.table())
+
     # ---- the experiment -----------------------------------------------------------------------------------------
     def evaluate(self, vertices, y, n_classes: Optional[int] = None, ratios: Sequence[float] = DEFAULT_RATIOS,
                  runs: int = 10, seed: int = 0, table: str = "Z", multilabel: bool = False,
@@ -549,3 +783,229 @@ class LabelProbe:
             out["fits"]["constant_columns"] = fit.constant.tolist()
             out.update(multilabel=True, predict=predict, constant_columns=int(fit.constant.sum()))
         return out
+
+
+# ---- a kept classifier ------------------------------------------------------------------------------------------
+MODEL_KEYS = ("W", "b", "class_names", "multilabel", "l2", "col_state", "d", "table", "n_train", "objective",
+              "iterations", "converged", "cv")
+
+
+@dataclass
+class LabelModel:
+    """One fitted classifier, on the host: what ``LabelProbe.train`` returns, a file keeps and ``predict_*`` apply."""
+    W: np.ndarray               # [C, d], the accumulate dtype of the table it was fitted on
+    b: np.ndarray               # [C]
+    class_names: List[str]
+    multilabel: bool
+    l2: float
+    col_state: Optional[np.ndarray]     # multi-label: int8 [C], -1 / +1 a class no / every labelled vertex has
+    d: int
+    table: str
+    n_train: int
+    objective: float
+    iterations: int
+    converged: bool
+    cv: Optional[dict] = None   # CrossValidation.table(), or None where l2 was given
+
+    def __post_init__(self):
+        self.check("LabelModel")
+
+    def check(self, what: str):
+        W, b, C = np.asarray(self.W), np.asarray(self.b), len(self.class_names)
+        if W.ndim != 2 or W.shape[1] != int(self.d) or b.shape != (W.shape[0],) or W.dtype != b.dtype \
+                or W.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: W {W.shape} {W.dtype} and b {b.shape} {b.dtype} are no [C, d = {self.d}] weights "
+                             f"with their [C] biases")
+        if C != W.shape[0]:
+            raise ValueError(f"{what}: {C} class names for the {W.shape[0]} classes of W")
+        if self.multilabel != (self.col_state is not None) or \
+                (self.col_state is not None and np.asarray(self.col_state).shape != (C,)):
+            raise ValueError(f"{what}: a multi-label model, and only it, carries col_state [C = {C}]")
+        if self.table not in ("Z", "X"):
+            raise ValueError(f"{what}: table must be 'Z' or 'X', got {self.table!r}")
+
+    @property
+    def C(self) -> int:
+        return len(self.class_names)
+
+    def save(self, path) -> Path:
+        """One ``.npz`` of MODEL_KEYS, read with numpy alone (no pickle: the names are a string array, cv is JSON)."""
+        path = Path(path)
+        state = np.zeros(0, dtype=np.int8) if self.col_state is None else np.asarray(self.col_state, dtype=np.int8)
+        with open(path, "wb") as io:
+            np.savez(io, W=self.W, b=self.b, class_names=np.array(self.class_names, dtype=np.str_),
+                     multilabel=np.bool_(self.multilabel), l2=np.float64(self.l2), col_state=state, d=np.int64(self.d),
+                     table=np.str_(self.table), n_train=np.int64(self.n_train), objective=np.float64(self.objective),
+                     iterations=np.int64(self.iterations), converged=np.bool_(self.converged),
+                     cv=np.str_(json.dumps(self.cv)))
+        return path
+
+    @classmethod
+    def load(cls, path, d: Optional[int] = None) -> "LabelModel":
+        """The model of ``save``; ``d``: the width it must have.  A file that is no such archive, a shape that does not
+        fit and a class-name count other than W's are a ValueError."""
+        name = os.fspath(path)
+        try:
+            with np.load(name) as z:
+                missing = [key for key in MODEL_KEYS if key not in z.files]
+                if missing:
+                    raise ValueError(f"LabelModel.load: {name!r} lacks {missing}")
+                multilabel = bool(z["multilabel"])
+                fields = dict(W=np.array(z["W"]), b=np.array(z["b"]), class_names=[str(c) for c in z["class_names"].reshape(-1)],
+                              multilabel=multilabel, l2=float(z["l2"]),
+                              col_state=np.array(z["col_state"], dtype=np.int8) if multilabel else None, d=int(z["d"]),
+                              table=str(z["table"]), n_train=int(z["n_train"]), objective=float(z["objective"]),
+                              iterations=int(z["iterations"]), converged=bool(z["converged"]), cv=json.loads(str(z["cv"])))
+        except ValueError:
+            raise
+        except Exception as e:                              # a truncated or foreign file: zipfile / numpy errors
+            raise ValueError(f"LabelModel.load: {name!r} is no label model: {type(e).__name__}: {e}") from None
+        try:
+            model = cls(**fields)
+        except ValueError as e:
+            raise ValueError(str(e).replace("LabelModel:", f"LabelModel.load: {name!r}:", 1)) from None
+        if d is not None and int(d) != model.d:
+            raise ValueError(f"LabelModel.load: {name!r} holds a model for d = {model.d}, not {int(d)}")
+        return model
+
+    # ---- applying it ------------------------------------------------------------------------------------------------
+    def _apply(self, engine, Z, rows, top: int, proba: bool):
+        if Z.dim() != 2 or int(Z.shape[1]) < self.d or int(engine.d) != self.d:
+            raise ValueError(f"the model was fitted for d = {self.d}; the engine has d = {engine.d} and the table rows of "
+                             f"{tuple(Z.shape)[1:]}")
+        out = LabelProbe(engine).predict(Z, rows, torch.from_numpy(np.ascontiguousarray(self.W)),
+                                         torch.from_numpy(np.ascontiguousarray(self.b)), self.C, top=top, proba=proba,
+                                         multilabel=self.multilabel, col_state=self.col_state)
+        res = (out.classes[:, 0].cpu().numpy(), out.probs[:, 0].cpu().numpy())
+        return res + (out.proba[:, 0].cpu().numpy(),) if proba else res
+
+    def predict_table(self, engine, vertices=None, table: str = "Z", top: int = 3, proba: bool = False):
+        """(classes [m, top] int32, probs [m, top][, proba [m, C]]) on the host for the vertices (default: all, in vertex
+        order) from the engine's table "Z" or "X"."""
+        if vertices is None:
+            vertices = torch.arange(engine.V)
+        Z, rows = table_and_rows(engine, vertices, table)
+        return self._apply(engine, Z, rows, top, proba)
+
+    def predict_rows(self, engine, M: torch.Tensor, top: int = 3, proba: bool = False):
+        """The same for the rows of ``M`` [m, d], a device tensor of the table's dtype (``NewVertexEmbedder.embed``'s
+        ``Z`` of new vertices, say), read with identity rows."""
+        if not isinstance(M, torch.Tensor) or M.dim() != 2 or M.dtype not in (torch.float32, torch.float64, torch.bfloat16):
+            raise ValueError("predict_rows: M must be a [m, d] tensor of dtype float32, float64 or bfloat16")
+        rows = torch.arange(M.shape[0], dtype=torch.int32, device=M.device)
+        return self._apply(engine, M, rows, top, proba)
+
+
+# ---- the CLI section `label_prediction` -------------------------------------------------------------------------------
+SECTION_KEYS = ("labels", "l2", "folds", "seed", "top", "multilabel", "scope", "load")
+
+
+def check_section(section, data_root, world_size: int = 1) -> dict:
+    """The validated ``label_prediction`` section of a config, file paths resolved against ``data_root``: ``{"labels",
+    "load" (Paths or None), "l2" (a float or a list), "folds", "seed", "top", "multilabel", "scope"}``.  Before any graph
+    is read."""
+    if world_size > 1:
+        raise NotImplementedError(
+            "label_prediction: fitting and applying a label model runs on ONE GPU only (WORLD_SIZE > 1): several GPUs "
+            "are out of scope")
+    if not isinstance(section, dict):
+        raise ValueError("label_prediction: expected a mapping with the key `labels` or `load`")
+    unknown = sorted(set(section) - set(SECTION_KEYS))
+    if unknown:
+        raise ValueError(f"label_prediction: unknown keys {unknown}; known: {list(SECTION_KEYS)}")
+    files = {}
+    for key in ("labels", "load"):
+        value = section.get(key)
+        if value is not None and (not isinstance(value, str) or not value):
+            raise ValueError(f"label_prediction: {key} must be a file name, got {value!r}")
+        files[key] = None if value is None else (Path(value) if Path(value).is_absolute() else Path(data_root) / value)
+    if (files["labels"] is None) == (files["load"] is None):
+        raise ValueError("label_prediction: give exactly one of `labels` (fit a model) and `load` (apply a saved one)")
+    fitting_only = sorted(set(section) & {"l2", "folds", "seed", "multilabel"})
+    if files["load"] is not None and fitting_only:
+        raise ValueError(f"label_prediction: {fitting_only} only steer a fit and have no effect on a loaded model (it "
+                         f"carries its own l2 and multilabel): leave them out with `load`")
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v >= 0   # noqa: E731
+    l2 = section.get("l2", 1.0)
+    if isinstance(l2, list):
+        if not l2 or not all(number(v) for v in l2) or len({float(v) for v in l2}) != len(l2):
+            raise ValueError(f"label_prediction: l2 must be a number >= 0 or a list of distinct ones, got {l2!r}")
+        l2 = [float(v) for v in l2]
+    elif number(l2):
+        l2 = float(l2)
+    else:
+        raise ValueError(f"label_prediction: l2 must be a number >= 0 or a list of distinct ones, got {l2!r}")
+    whole = lambda v: isinstance(v, int) and not isinstance(v, bool)    # noqa: E731
+    folds = section.get("folds", 5)
+    if not whole(folds) or folds < 2:
+        raise ValueError(f"label_prediction: folds must be an integer >= 2, got {folds!r}")
+    if "folds" in section and not isinstance(l2, list):
+        raise ValueError("label_prediction: folds is given but l2 is no list: nothing is cross-validated")
+    seed = section.get("seed", 0)
+    if not whole(seed):
+        raise ValueError(f"label_prediction: seed must be an integer, got {seed!r}")
+    top = section.get("top", 3)
+    if not whole(top) or not 1 <= top <= _hip.PREDICT_MAX_TOP:
+        raise ValueError(f"label_prediction: top must be an integer in 1..{_hip.PREDICT_MAX_TOP}, got {top!r}")
+    multilabel = section.get("multilabel", False)
+    if not isinstance(multilabel, bool):
+        raise ValueError(f"label_prediction: multilabel must be true or false, got {multilabel!r}")
+    scope = section.get("scope", "unlabelled")
+    if scope not in ("unlabelled", "all"):
+        raise ValueError(f"label_prediction: scope must be 'unlabelled' or 'all', got {scope!r}")
+    for key, path in files.items():
+        if path is not None and not path.is_file():
+            raise FileNotFoundError(f"label_prediction: the {key} file {str(path)!r} is missing")
+    return {"labels": files["labels"], "load": files["load"], "l2": l2, "folds": folds, "seed": seed, "top": top,
+            "multilabel": multilabel, "scope": scope}
+
+
+def write_predictions_tsv(path, ids: Sequence[str], class_names: Sequence[str], classes: np.ndarray,
+                          probs: np.ndarray) -> int:
+    """``id<TAB>class<TAB>prob[<TAB>class<TAB>prob]...`` per row, class NAMES best first, probabilities as ``repr`` of
+    the float; slots without a class (-1) are left out.  Returns the number of lines."""
+    with open(path, "w") as io:
+        for vid, cs, ps in zip(ids, classes.tolist(), probs.tolist()):
+            io.write("\t".join([str(vid)] + [f"{class_names[c]}\t{float(q)!r}" for c, q in zip(cs, ps) if c >= 0]) + "\n")
+    return len(ids)
+
+
+def run_section(cfg: dict, graph, output_root, say=print) -> Tuple["LabelModel", dict]:
+    """What the CLI does for a checked ``label_prediction`` section after ``Z.npy``: fit (or load) the model, write
+    ``label_model.npz`` (fitted models only), ``predicted_labels.tsv`` and return (model, the report that becomes
+    ``label_prediction.json`` -- the caller adds the arrivals' count and writes it)."""
+    output_root = Path(output_root)
+    predicted = np.ones(len(graph), dtype=bool)
+    if cfg["load"] is not None:
+        model = LabelModel.load(cfg["load"], d=graph.d)
+        source = "loaded"
+    else:
+        labelled, y, names = read_labels(cfg["labels"], graph.vertex_ids, multilabel=cfg["multilabel"])
+        model = LabelProbe(graph.engine()).train(labelled, y, len(names), l2=cfg["l2"], folds=cfg["folds"],
+                                                 seed=cfg["seed"], multilabel=cfg["multilabel"], class_names=names)
+        model.save(output_root / "label_model.npz")
+        if cfg["scope"] == "unlabelled":
+            predicted[labelled] = False
+        source = "fitted"
+    vertices = np.flatnonzero(predicted)
+    if len(vertices):
+        _, classes, probs = graph.predict_labels(model, vertices, top=cfg["top"])
+    else:
+        classes, probs = np.zeros((0, cfg["top"]), np.int32), np.zeros((0, cfg["top"]), np.float32)
+    write_predictions_tsv(output_root / "predicted_labels.tsv", [graph.vertex_ids[v] for v in vertices],
+                          model.class_names, classes, probs)
+    hist = np.histogram(probs[:, 0].astype(np.float64), bins=10, range=(0.0, 1.0))[0] if len(vertices) else np.zeros(10)
+    report = {"model": source, "labelled": int(model.n_train), "predicted": int(len(vertices)), "scope": cfg["scope"],
+              "class_names": list(model.class_names), "multilabel": bool(model.multilabel), "l2": float(model.l2),
+              "cv": model.cv, "iterations": int(model.iterations), "converged": bool(model.converged),
+              "objective": float(model.objective), "top": cfg["top"],
+              "top1_probability_histogram": [int(c) for c in hist]}
+    return model, report
+
+
+def write_report(output_root, report: dict) -> Path:
+    out = Path(output_root) / "label_prediction.json"
+    with open(out, "w") as io:
+        json.dump(report, io, indent=1)
+        io.write("\n")
+    return out

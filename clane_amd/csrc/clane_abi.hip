@@ -14,6 +14,7 @@
 #include "edge_score.h"
 #include "device_utils.h"
 #include "kmeans.h"
+#include "label_predict.h"
 #include "label_probe.h"
 #include "multilabel_probe.h"
 #include "new_rows.h"
@@ -1058,6 +1059,40 @@ int probe_grad(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int
     return check_launch("probe_grad");
 }
 
+// Applying fitted probes (label_predict.h): probe_forward's launch shape, probabilities and the top-m classes out.
+template <typename T, typename A>
+int probe_predict(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *W,
+                  const A *bias, const int8_t *col_state, int32_t F, int32_t C, int32_t top_m, int32_t flags,
+                  int32_t *top_class, A *top_prob, A *proba, void *stream) {
+    static_assert(kPredictSigmoid == CLANE_PREDICT_SIGMOID && kPredictWriteProba == CLANE_PREDICT_WRITE_PROBA &&
+                      kPredictMaxTop == CLANE_PREDICT_MAX_TOP,
+                  "header and kernel disagree");
+    REQUIRE(table_rows >= 0 && n >= 0 && d > 0 && d <= 32768 && ldz >= d,
+            "probe_predict: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    REQUIRE((flags & ~(CLANE_PREDICT_SIGMOID | CLANE_PREDICT_WRITE_PROBA)) == 0, "probe_predict: unknown flags %d", flags);
+    const bool sigmoid = (flags & CLANE_PREDICT_SIGMOID) != 0;
+    REQUIRE(C >= (sigmoid ? 1 : 2) && C <= kProbeMaxClasses, "probe_predict: C must be in [%d, %d], got %d",
+            sigmoid ? 1 : 2, kProbeMaxClasses, C);
+    REQUIRE(top_m >= 1 && top_m <= kPredictMaxTop, "probe_predict: top_m must be in [1, %d], got %d", kPredictMaxTop,
+            top_m);
+    const int cp_log = probe_cp_log(C);
+    REQUIRE(F >= 1 && F <= (INT32_MAX >> 7), "probe_predict: bad number of fits %d", F);
+    REQUIRE(Z && rows && W && bias && top_class && top_prob, "probe_predict: null pointer");
+    REQUIRE(!sigmoid || col_state, "probe_predict: CLANE_PREDICT_SIGMOID needs col_state");
+    REQUIRE(!(flags & CLANE_PREDICT_WRITE_PROBA) || proba, "probe_predict: CLANE_PREDICT_WRITE_PROBA needs proba");
+    const int K = F << cp_log;
+    const int n_tiles = int(ceil_div(int64_t(K), int64_t(kProjBN)));
+    const int64_t row_tiles = n > 0 ? probe_row_tiles(n) : 0;
+    const int64_t blocks = row_tiles * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "probe_predict: %lld rows x %d fits is too many for one launch", (long long)n, F);
+    if (blocks == 0) return CLANE_OK;
+    probe_predict_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(
+        Z, table_rows, d, ldz, rows, n, W, bias, col_state, F, C, cp_log, top_m, flags, top_class, top_prob, proba,
+        n_tiles);
+    return check_launch("probe_predict");
+}
+
 // ---- node clustering (kmeans.h) ---------------------------------------------------------------------------------------
 inline int64_t kmeans_windows(int64_t n, int64_t R) { return ceil_div(n > 0 && R > 0 ? n * R : 1, int64_t(kKmChunk)); }
 
@@ -1778,6 +1813,13 @@ CLANE_EMBED_WRAPPERS(bf16, uint16_t, bf16_t, float, float)
                                int64_t n, const AT *G, int32_t K, AT *ws, AT *dW, AT *db, void *stream) {              \
         return probe_grad<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, G, K, ws, dW, db,        \
                                  stream);                                                                              \
+    }                                                                                                                  \
+    int clane_probe_predict_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \
+                                  int64_t n, const AT *W, const AT *bias, const int8_t *col_state, int32_t F,          \
+                                  int32_t C, int32_t top_m, int32_t flags, int32_t *top_class, AT *top_prob,           \
+                                  AT *proba, void *stream) {                                                           \
+        return probe_predict<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, W, bias, col_state,   \
+                                    F, C, top_m, flags, top_class, top_prob, proba, stream);                           \
     }
 CLANE_PROBE_WRAPPERS(f32, float, float, float)
 CLANE_PROBE_WRAPPERS(f64, double, double, double)

@@ -539,6 +539,33 @@ class Graph(torch.utils.data.Dataset):
         res.Z = res.Z.to(self.X.dtype).contiguous()
         return res
 
+    def _resolve_labels(self, labels, multilabel: bool, what: str):
+        """(vertex indices, classes or class-set masks, sorted class names) from the three forms ``evaluate_labels``
+        takes."""
+        from .classify import index_classes, read_labels
+        if isinstance(labels, (str, Path)):
+            return read_labels(Path(labels), self.vertex_ids, multilabel=bool(multilabel))
+        if isinstance(labels, tuple) and len(labels) == 2:
+            vertices, raw = list(labels[0]), list(labels[1])
+        else:
+            raw = list(labels)
+            vertices = list(range(len(self)))
+        if len(raw) != len(vertices):
+            raise ValueError(f"{what}: one class per labelled vertex")
+        item = lambda c: c.item() if isinstance(c, torch.Tensor) else c     # noqa: E731
+        if multilabel:
+            if any(isinstance(s, (str, bytes)) or not hasattr(s, "__iter__") for s in raw):
+                raise ValueError(f"{what}: multilabel needs a collection of classes per labelled vertex")
+            sets = [[item(c) for c in s] for s in raw]
+            names = sorted({c for s in sets for c in s})
+            if len(names) > 64:
+                raise ValueError(f"{what}: {len(names)} classes; the multi-label probe handles at most 64")
+            index = {c: i for i, c in enumerate(names)}
+            y = [sum(1 << index[c] for c in set(s)) for s in sets]
+        else:
+            y, names = index_classes([item(c) for c in raw])
+        return vertices, y, names
+
     def evaluate_labels(self, labels, ratios=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), runs: int = 10, seed: int = 0,
                         l2: float = 1.0, table: str = "Z", multilabel: bool = False, predict: str = "top_k") -> dict:
         """The reference README's node-classification table for the CURRENT embeddings (extension): a soft-max regression
@@ -556,36 +583,44 @@ class Graph(torch.utils.data.Dataset):
         highest score (``predict="top_k"``) or those of positive score (``"threshold"``).  The result also has
         ``"multilabel"``, ``"predict"`` and ``"constant_columns"`` (class columns of a fit that no or every training
         vertex has: not fitted, predicted never / always)."""
-        from .classify import LabelProbe, index_classes, read_labels
+        from .classify import LabelProbe
         if predict not in ("top_k", "threshold"):
             raise ValueError(f"evaluate_labels: predict must be 'top_k' or 'threshold', got {predict!r}")
-        if isinstance(labels, (str, Path)):
-            vertices, y, names = read_labels(Path(labels), self.vertex_ids, multilabel=bool(multilabel))
-        else:
-            if isinstance(labels, tuple) and len(labels) == 2:
-                vertices, raw = list(labels[0]), list(labels[1])
-            else:
-                raw = list(labels)
-                vertices = list(range(len(self)))
-            if len(raw) != len(vertices):
-                raise ValueError("evaluate_labels: one class per labelled vertex")
-            item = lambda c: c.item() if isinstance(c, torch.Tensor) else c     # noqa: E731
-            if multilabel:
-                if any(isinstance(s, (str, bytes)) or not hasattr(s, "__iter__") for s in raw):
-                    raise ValueError("evaluate_labels: multilabel needs a collection of classes per labelled vertex")
-                sets = [[item(c) for c in s] for s in raw]
-                names = sorted({c for s in sets for c in s})
-                if len(names) > 64:
-                    raise ValueError(f"evaluate_labels: {len(names)} classes; the multi-label probe handles at most 64")
-                index = {c: i for i, c in enumerate(names)}
-                y = [sum(1 << index[c] for c in set(s)) for s in sets]
-            else:
-                y, names = index_classes([item(c) for c in raw])
+        vertices, y, names = self._resolve_labels(labels, multilabel, "evaluate_labels")
         kw = dict(multilabel=True, predict=predict) if multilabel else {}
         out = LabelProbe(self.engine(), l2=l2).evaluate(vertices, y, len(names), ratios=tuple(ratios), runs=runs,
                                                         seed=seed, table=table, **kw)
         out["class_names"] = [str(c) for c in names]
         return out
+
+    def fit_labels(self, labels, l2=1.0, folds: int = 5, seed: int = 0, table: str = "Z", multilabel: bool = False):
+        """A kept classifier on the CURRENT embeddings (extension, classify.py): a soft-max regression (``multilabel``:
+        one-vs-rest regressions) on ALL labelled vertices, returned as a ``classify.LabelModel`` with ``save`` / ``load``.
+        ``labels`` as ``evaluate_labels`` takes them.  ``l2``: a number, or a list -- then the value of lowest mean
+        held-out log-loss over ``folds`` folds (one permutation seeded ``seed``) is chosen, every fold and value fitted
+        at once, and the model's ``cv`` holds the table.  Several GPUs and a column division raise
+        NotImplementedError."""
+        from .classify import LabelProbe
+        vertices, y, names = self._resolve_labels(labels, multilabel, "fit_labels")
+        l2 = list(l2) if isinstance(l2, (list, tuple)) else float(l2)
+        return LabelProbe(self.engine()).train(vertices, y, len(names), l2=l2, folds=folds, seed=seed, table=table,
+                                               multilabel=bool(multilabel), class_names=[str(c) for c in names])
+
+    def predict_labels(self, model, vertices=None, top: int = 3, table: Optional[str] = None, proba: bool = False):
+        """(vertex indices, classes [m, top], probs [m, top][, proba [m, C]]) on the host: the ``top`` most probable
+        classes of the vertices (default: all) under ``model`` (``fit_labels`` / ``LabelModel.load``), best first, as
+        indices into ``model.class_names``; -1 / 0 where the model has fewer classes to give.  Probabilities are a
+        soft-max over the classes, or per-class sigmoids that do not sum to 1 for a multi-label model.  ``table``: the
+        model's own by default.  A model of another width is a ValueError; several GPUs raise NotImplementedError."""
+        from .classify import LabelProbe
+        d = int(self.X.shape[1])
+        if int(model.d) != d:
+            raise ValueError(f"predict_labels: the model was fitted for d = {model.d}, this graph has d = {d}")
+        eng = self.engine()
+        LabelProbe(eng)                                     # the probe's refusals: one GPU, no column division
+        v = np.arange(len(self), dtype=np.int64) if vertices is None else np.asarray(list(vertices), dtype=np.int64)
+        return (v,) + tuple(model.predict_table(eng, v, table=model.table if table is None else table, top=top,
+                                                proba=proba))
 
     def cluster(self, k=None, labels=None, vertices=None, restarts: int = 10, seed: int = 0, max_iter: int = 300,
                 table: str = "Z", return_assignments: bool = False, silhouette: bool = False,

@@ -84,7 +84,10 @@ extern "C" {
                              *    clane_tsne_nn_attract_f32, clane_tsne_repulse_f32 (neighbour-sparse 2-D layout: the k
                              *    nearest listed rows of every listed row with the selection fused into the distances, P
                              *    on those neighbours only, the repulsion exact; clane_tsne_step_f32 takes up to
-                             *    CLANE_TSNE_NN_MAX_POINTS points) */
+                             *    CLANE_TSNE_NN_MAX_POINTS points)
+                             *    + clane_probe_predict_* (applying fitted probes: class probabilities and the top-m classes
+                             *    of rows of the table under F stacked soft-max or one-vs-rest models, fused into the logits'
+                             *    contraction) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -736,6 +739,35 @@ int clane_probe_forward_ovr_bf16(const uint16_t *Z, int64_t table_rows, int32_t 
                                  const float *bias, const int8_t *col_state, int32_t F, int32_t C, int32_t max_labels,
                                  int32_t flags, float *G, double *loss_ws, double *loss, uint64_t *pred, int64_t ld_pred,
                                  void *stream);
+
+/* ---- applying fitted probes (csrc/label_predict.h) ---------------------------------------------------------------------
+ * Class probabilities and the top_m classes of the rows `rows[0..n)` of the table Z (an index outside [0, table_rows) reads
+ * as a zero row) under F stacked models: W [K, d] and bias [K] as above, K = F * Cp.  The logits never reach memory.
+ *   soft-max (default, 2 <= C): p_c = exp(l_c - max) / sum exp(l - max) over the C real classes, with the reductions and the
+ *     order of operations of clane_probe_forward_*: p_c - [c == y] equals its G for a training row bit for bit.  A class's
+ *     value is l_c.
+ *   CLANE_PREDICT_SIGMOID (one-vs-rest models, 1 <= C): p_c = sigmoid(l_c) per column as in clane_probe_forward_ovr_*;
+ *     col_state [K] (int8) as there: a column of state -1 / +1 has value -inf / +inf and p = 0 / 1.
+ *   top_class [n, F, top_m] (int32) and top_prob [n, F, top_m] (accumulate type), 1 <= top_m <= CLANE_PREDICT_MAX_TOP: the
+ *     classes of highest value, best first, ties to the lowest class, a NaN or -inf value never; where fewer than top_m
+ *     classes are eligible the rest is -1 and 0.
+ *   proba [n, F, C] (accumulate type; CLANE_PREDICT_WRITE_PROBA): the probability of every real class.
+ * No atomics: two calls give the same bits, and a fit's results do not depend on the other fits of the call. */
+#define CLANE_PREDICT_SIGMOID 1
+#define CLANE_PREDICT_WRITE_PROBA 2
+#define CLANE_PREDICT_MAX_TOP 8
+int clane_probe_predict_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const float *W, const float *bias, const int8_t *col_state, int32_t F, int32_t C,
+                            int32_t top_m, int32_t flags, int32_t *top_class, float *top_prob, float *proba,
+                            void *stream);
+int clane_probe_predict_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const double *W, const double *bias, const int8_t *col_state, int32_t F, int32_t C,
+                            int32_t top_m, int32_t flags, int32_t *top_class, double *top_prob, double *proba,
+                            void *stream);
+int clane_probe_predict_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const float *W, const float *bias, const int8_t *col_state, int32_t F, int32_t C,
+                             int32_t top_m, int32_t flags, int32_t *top_class, float *top_prob, float *proba,
+                             void *stream);
 
 /* ---- node clustering (csrc/kmeans.h) ----------------------------------------------------------------------------------
  * One Lloyd iteration of k-means for R restarts at once on the rows `rows[0..n)` of the table Z (an index outside
