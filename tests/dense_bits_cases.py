@@ -18,6 +18,9 @@ The host file feeds assert_* with dots summed in two different orders on the CPU
 Planted exact ties (the positions of the integer-data tie tests): table row 5 is also row 133 and row 290, centre 3 also
 7 and 131, class 1 of every probe fit also class 2 and, where Cp = 64, class 17, and class 3 also class 40.  On float
 data such a tie survives only if the bits do not depend on the position.
+
+Sibling: tests/distance_bits_cases.py holds relations 9..13 (silhouette_norms, silhouette_sums, tsne_sqdist, knn_sqdist,
+probe_predict) to the same anchor, with this module's fixtures.
 """
 import functools
 
