@@ -132,6 +132,15 @@ def embedding(args):
         label_pred = classify.check_section(hparams["label_prediction"], Path(args.data_root),
                                             int(os.environ.get("WORLD_SIZE", "1")))
 
+    # optional section (extension): soft_clustering: {clusters: 5 | [..], labels: Y, restarts: 10, seed: 0, max_iter: 100,
+    # tol: 0.001, reg_covar: 1.0e-6, criterion: bic | aic, baseline: true, memberships: true, top: 3} -- a Gaussian
+    # mixture on the embeddings the run ends with (mixture.py); checked before the graph loads
+    soft_clu = None
+    if isinstance(hparams, dict) and "soft_clustering" in hparams:
+        from . import mixture
+        soft_clu = mixture.check_section(hparams["soft_clustering"], Path(args.data_root),
+                                         int(os.environ.get("WORLD_SIZE", "1")))
+
     rank, world = _distributed_setup()
     say = print if rank == 0 else (lambda *a, **k: None)      # every rank computes; rank 0 talks and writes
     say('[Embedding]', end='\n')
@@ -338,6 +347,14 @@ def embedding(args):
         say(f"The clustering of {first['clustered']} vertices into {first['clusters']} clusters is stored in "
             f"{out.absolute()}.")
 
+    mixture_model = mixture_report = None
+    if soft_clu is not None:                        # a Gaussian mixture on the embeddings the run ends with
+        from . import mixture
+        mixture_model, mixture_report = mixture.run_section(soft_clu, g, args.output_root)
+        mixture.write_report(args.output_root, mixture_report)      # written again below with the arrivals' count
+        say(f"The soft clustering of {mixture_report['clustered']} vertices into {mixture_report['clusters']} components "
+            f"is stored in {args.output_root.joinpath('mixture_metrics.json').absolute()}.")
+
     if layout_cfg is not None:                      # the picture of the embeddings the run ends with
         from . import layout as layout_mod
         kw = {key: layout_cfg[key] for key in ("perplexity", "max_points", "max_iter", "seed", "method", "neighbours")
@@ -368,6 +385,14 @@ def embedding(args):
             label_report["predicted_new"] = classify.write_predictions_tsv(
                 args.output_root.joinpath('predicted_labels_new.tsv'), new_ids, label_model.class_names, classes, probs)
             classify.write_report(args.output_root, label_report)
+        if mixture_model is not None:               # the same mixture on the arrivals, in the order of their V
+            from . import mixture
+            eng = g.engine()
+            comp, prob = mixture_model.predict_rows(eng, res.Z.to(eng.device, eng.Zcur.dtype).contiguous(),
+                                                    top=soft_clu["top"])
+            mixture_report["assigned_new"] = mixture.write_memberships_tsv(
+                args.output_root.joinpath('memberships_new.tsv'), new_ids, comp, prob)
+            mixture.write_report(args.output_root, mixture_report)
 
 
 def _to_numpy(Z: torch.Tensor) -> np.ndarray:

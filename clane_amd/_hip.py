@@ -129,6 +129,14 @@ for _s in ("f32", "f64", "bf16"):   # node clustering (csrc/kmeans.h)
     SIGNATURES[f"clane_kmeans_update_{_s}"] = (
         C.c_int, [_p, _i64, _i32, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p])
 SIGNATURES["clane_kmeans_update_ws_len"] = (_i64, [_i64, _i32, _i32, _i32])
+MIXTURE_MAX_COMPONENTS = 64         # CLANE_MIXTURE_MAX_COMPONENTS
+MIXTURE_WRITE_RESP, MIXTURE_WRITE_ASSIGN = 1, 2
+for _s in ("f32", "f64", "bf16"):   # Gaussian mixtures (csrc/mixture.h)
+    SIGNATURES[f"clane_mixture_estep_{_s}"] = (
+        C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p])
+    SIGNATURES[f"clane_mixture_mstep_{_s}"] = (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _p, _p, _i32, _p, _p, _p, _p])
+SIGNATURES["clane_mixture_ll_ws_len"] = (_i64, [_i64, _i32])
+SIGNATURES["clane_mixture_mstep_ws_len"] = (_i64, [_i64, _i32, _i32])
 for _s in ("f32", "f64", "bf16"):   # new vertices against the finished table (csrc/new_rows.h)
     _g = C.c_double if _s == "f64" else C.c_float
     SIGNATURES[f"clane_embed_rows_{_s}"] = (
@@ -186,6 +194,13 @@ def ovr_padded_classes(C_: int) -> int:
     if not 1 <= int(C_) <= PROBE_MAX_CLASSES:
         raise ValueError(f"the multi-label probe handles 1..{PROBE_MAX_CLASSES} classes, got {C_}")
     return 1 << (int(C_) - 1).bit_length()
+
+
+def mixture_padded_components(K_: int) -> int:
+    """Kp: the columns a restart takes in the stacked mixture parameters -- K rounded up to a power of two (1..64)."""
+    if not 1 <= int(K_) <= MIXTURE_MAX_COMPONENTS:
+        raise ValueError(f"the Gaussian mixture handles 1..{MIXTURE_MAX_COMPONENTS} components, got {K_}")
+    return 1 << (int(K_) - 1).bit_length()
 
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
@@ -602,6 +617,24 @@ class KernelBackend(abc.ABC):
         """centres_new[r, j] = the mean of the table rows order[seg[r K + j] : seg[r K + j + 1]] (the old centre where
         the segment is empty), csq_new its squared norm.  order holds restart r's n rows at [r n, (r + 1) n)."""
         raise NotImplementedError(f"{type(self).__name__} has no kmeans_update")
+
+    # soft clusters (mixture.py): optional in the same way -- GaussianMixture is the only caller.  rows are TABLE ROWS
+    # (int32); mean [d], Wm [R * Kp, 2 d], cst [R * Kp], resp [n, R * Kp], S and nk in the accumulate dtype.
+    def mixture_ll_ws_len(self, n: int, R: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no mixture_ll_ws_len")
+
+    def mixture_estep(self, Z, d: int, rows, mean, Wm, cst, R: int, K: int, ll_ws, ll, resp=None, assign=None):
+        """With xc = Z[rows[i], :d] - mean and l = [xc^2 | xc] . Wm_r^T + cst_r over restart r's K real components:
+        ll[r] = sum_i logsumexp(l) (float64 [R]); with ``resp`` ([n, R * Kp]) also the responsibilities exp(l - lse), pad
+        columns 0; with ``assign`` (int32, [n, >= R]) the arg-max component, ties to the lowest."""
+        raise NotImplementedError(f"{type(self).__name__} has no mixture_estep")
+
+    def mixture_mstep_ws_len(self, n: int, K: int, d: int) -> int:
+        raise NotImplementedError(f"{type(self).__name__} has no mixture_mstep_ws_len")
+
+    def mixture_mstep(self, Z, d: int, rows, mean, resp, ws, S, nk):
+        """S [K, 2 d] = resp^T . [xc^2 | xc] and nk [K] = the column sums of resp, K = the columns of resp."""
+        raise NotImplementedError(f"{type(self).__name__} has no mixture_mstep")
 
     # content reduction (reduce.py): optional in the same way -- ContentPCA is the only caller.  rows are TABLE ROWS
     # (int32; an entry outside the table is an absent row); mu, W, G and the Gram's workspace in the accumulate dtype.
@@ -1446,6 +1479,53 @@ class HipKernels(KernelBackend):
                      zp, Z.shape[0], d, ldz, _vec(order, torch.int32, "order"), _vec(seg, torch.int64, "seg"), n, R, K,
                      _vec(centres_old, acc, "centres_old"), _vec(ws, acc, "ws"), _vec(centres_new, acc, "centres_new"),
                      _vec(csq_new, acc, "csq_new"), self._stream(Z))
+
+    # -- soft clusters ---------------------------------------------------------------------
+    def mixture_ll_ws_len(self, n: int, R: int) -> int:
+        return int(self.lib.clane_mixture_ll_ws_len(n, R))
+
+    def mixture_mstep_ws_len(self, n: int, K: int, d: int) -> int:
+        return int(self.lib.clane_mixture_mstep_ws_len(n, K, d))
+
+    def mixture_estep(self, Z, d: int, rows, mean, Wm, cst, R: int, K: int, ll_ws, ll, resp=None, assign=None):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n = rows.numel()
+        Kt = R * mixture_padded_components(K)
+        if Z.shape[1] < d or rows.dim() != 1 or mean.numel() != d:
+            raise ValueError(f"mixture_estep: Z must have at least d = {d} columns, rows be a vector and mean [{d}]")
+        if tuple(Wm.shape) != (Kt, 2 * d) or cst.numel() != Kt:
+            raise ValueError(f"mixture_estep: Wm must be [R * Kp, 2 d] = [{Kt}, {2 * d}] and cst [{Kt}], got "
+                             f"{tuple(Wm.shape)}, {tuple(cst.shape)}")
+        if ll.numel() < R or ll_ws.numel() < self.mixture_ll_ws_len(n, R):
+            raise ValueError("mixture_estep: ll needs R doubles, ll_ws mixture_ll_ws_len(n, R)")
+        flags, rp, ap, lda = 0, None, None, 0
+        if resp is not None:
+            if resp.numel() < n * Kt:
+                raise ValueError("mixture_estep: resp needs n * R * Kp elements")
+            flags, rp = flags | MIXTURE_WRITE_RESP, _vec(resp, acc, "resp")
+        if assign is not None:
+            ap, lda = _mat(assign, "assign")
+            if assign.dtype != torch.int32 or assign.shape[0] < n or assign.shape[1] < R:
+                raise ValueError("mixture_estep: assign must be int32 [n, >= R]")
+            flags |= MIXTURE_WRITE_ASSIGN
+        self._invoke(self._fn("clane_mixture_estep", Z.dtype), "clane_mixture_estep",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(mean, acc, "mean"),
+                     _vec(Wm, acc, "Wm"), _vec(cst, acc, "cst"), R, K, flags, rp, _vec(ll_ws, torch.float64, "ll_ws"),
+                     _vec(ll, torch.float64, "ll"), ap, lda, self._stream(Z))
+
+    def mixture_mstep(self, Z, d: int, rows, mean, resp, ws, S, nk):
+        zp, ldz = _mat(Z, "Z")
+        acc = acc_dtype(Z.dtype)
+        n, K = rows.numel(), nk.numel()
+        if Z.shape[1] < d or rows.dim() != 1 or mean.numel() != d:
+            raise ValueError(f"mixture_mstep: Z must have at least d = {d} columns, rows be a vector and mean [{d}]")
+        if resp.numel() < n * K or S.numel() != K * 2 * d or ws.numel() < self.mixture_mstep_ws_len(n, K, d):
+            raise ValueError("mixture_mstep: resp needs n * K elements, S K * 2 d, nk K, ws mixture_mstep_ws_len(n, K, d)")
+        self._invoke(self._fn("clane_mixture_mstep", Z.dtype), "clane_mixture_mstep",
+                     zp, Z.shape[0], d, ldz, _vec(rows, torch.int32, "rows"), n, _vec(mean, acc, "mean"),
+                     _vec(resp, acc, "resp"), K, _vec(ws, acc, "ws"), _vec(S, acc, "S"), _vec(nk, acc, "nk"),
+                     self._stream(Z))
 
     # -- content reduction -----------------------------------------------------------------
     def column_sums_ws_len(self, n: int, d: int) -> int:

@@ -20,6 +20,7 @@
 #include "new_rows.h"
 #include "link_eval.h"
 #include "link_rank.h"
+#include "mixture.h"
 #include "pair_train.h"
 #include "projection.h"
 #include "sparse_rows.h"
@@ -1093,6 +1094,64 @@ int probe_predict(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const 
     return check_launch("probe_predict");
 }
 
+// ---- Gaussian mixtures (mixture.h): the probes' launch shapes over the 2 d wide operand [xc^2 | xc] --------------------
+template <typename T, typename A>
+int mixture_estep(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *mean,
+                  const A *Wm, const A *cst, int32_t R, int32_t K, int32_t flags, A *resp, double *ll_ws, double *ll,
+                  int32_t *assign, int64_t ld_assign, void *stream) {
+    static_assert(kMixtureWriteResp == CLANE_MIXTURE_WRITE_RESP && kMixtureWriteAssign == CLANE_MIXTURE_WRITE_ASSIGN &&
+                      kProbeMaxClasses == CLANE_MIXTURE_MAX_COMPONENTS,
+                  "header and kernel disagree");
+    // any d >= 1 whose depth 2 d, and the k loop's 2 d + 16, is an int
+    REQUIRE(table_rows >= 0 && n >= 0 && d >= 1 && d <= (INT32_MAX >> 2) && ldz >= d,
+            "mixture_estep: bad shape rows=%lld n=%lld d=%d ldz=%lld", (long long)table_rows, (long long)n, d,
+            (long long)ldz);
+    REQUIRE(K >= 1 && K <= kProbeMaxClasses, "mixture_estep: K must be in [1, %d], got %d", kProbeMaxClasses, K);
+    const int cp_log = probe_cp_log(K);
+    REQUIRE(R >= 1 && R <= (INT32_MAX >> 7), "mixture_estep: bad number of restarts %d", R);
+    REQUIRE((flags & ~(CLANE_MIXTURE_WRITE_RESP | CLANE_MIXTURE_WRITE_ASSIGN)) == 0, "mixture_estep: unknown flags %d",
+            flags);
+    REQUIRE(!(flags & CLANE_MIXTURE_WRITE_ASSIGN) || ld_assign >= R, "mixture_estep: ld_assign %lld < R = %d",
+            (long long)ld_assign, R);
+    REQUIRE(ll_ws && ll, "mixture_estep: null likelihood workspace/output");
+    REQUIRE(n == 0 || (Z && rows && mean && Wm && cst), "mixture_estep: null pointer");
+    REQUIRE(n == 0 || !(flags & CLANE_MIXTURE_WRITE_RESP) || resp, "mixture_estep: CLANE_MIXTURE_WRITE_RESP needs resp");
+    REQUIRE(n == 0 || !(flags & CLANE_MIXTURE_WRITE_ASSIGN) || assign,
+            "mixture_estep: CLANE_MIXTURE_WRITE_ASSIGN needs assign");
+    const int Kt = R << cp_log;
+    const int n_tiles = int(ceil_div(int64_t(Kt), int64_t(kProjBN)));
+    const int64_t row_tiles = n > 0 ? probe_row_tiles(n) : 0;
+    const int64_t blocks = row_tiles * n_tiles;
+    REQUIRE(blocks <= INT32_MAX, "mixture_estep: %lld rows x %d restarts is too many for one launch", (long long)n, R);
+    if (blocks > 0)
+        mixture_estep_kernel<T, A><<<unsigned(blocks), kBlock, 0, (hipStream_t)stream>>>(
+            Z, table_rows, d, ldz, rows, n, mean, Wm, cst, R, K, cp_log, flags, resp, ll_ws, assign, ld_assign, n_tiles);
+    probe_loss_reduce_kernel<<<unsigned(R), kBlock, 0, (hipStream_t)stream>>>(ll_ws, row_tiles, R, ll);
+    return check_launch("mixture_estep");
+}
+
+template <typename T, typename A>
+int mixture_mstep(const T *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n, const A *mean,
+                  const A *resp, int32_t K, A *ws, A *S, A *nk, void *stream) {
+    REQUIRE(table_rows >= 0 && n >= 0 && d >= 1 && d <= (INT32_MAX >> 2) && ldz >= d && K >= 1,
+            "mixture_mstep: bad shape rows=%lld n=%lld d=%d ldz=%lld K=%d", (long long)table_rows, (long long)n, d,
+            (long long)ldz, K);
+    REQUIRE(ws && S && nk, "mixture_mstep: null workspace/output");
+    REQUIRE(n == 0 || (Z && rows && mean && resp), "mixture_mstep: null pointer");
+    const int64_t n_chunks = n > 0 ? probe_grad_chunks(n) : 0;
+    REQUIRE(n_chunks <= 65535, "mixture_mstep: %lld rows is too many for one launch", (long long)n);
+    const int64_t d_tiles = ceil_div(int64_t(2 * d), int64_t(kProjBN)), k_tiles = ceil_div(int64_t(K), int64_t(kProjBM));
+    REQUIRE(d_tiles * k_tiles <= INT32_MAX, "mixture_mstep: K=%d x d=%d is too many tiles for one launch", K, d);
+    const int64_t len = int64_t(K) * (2 * int64_t(d) + 1);
+    if (n_chunks > 0)
+        mixture_mstep_kernel<T, A><<<dim3(unsigned(d_tiles * k_tiles), unsigned(n_chunks)), kBlock, 0,
+                                     (hipStream_t)stream>>>(Z, table_rows, d, ldz, rows, n, mean, resp, K, ws,
+                                                            int(d_tiles));
+    probe_grad_reduce_kernel<A><<<unsigned(ceil_div(len, kBlock)), kBlock, 0, (hipStream_t)stream>>>(
+        ws, n_chunks, len, int64_t(K) * 2 * d, S, nk);
+    return check_launch("mixture_mstep");
+}
+
 // ---- node clustering (kmeans.h) ---------------------------------------------------------------------------------------
 inline int64_t kmeans_windows(int64_t n, int64_t R) { return ceil_div(n > 0 && R > 0 ? n * R : 1, int64_t(kKmChunk)); }
 
@@ -1828,6 +1887,29 @@ CLANE_PROBE_WRAPPERS(bf16, uint16_t, bf16_t, float)
 int64_t clane_probe_loss_ws_len(int64_t n, int32_t F) { return probe_row_tiles(n) * (F > 0 ? F : 0); }
 int64_t clane_probe_grad_ws_len(int64_t n, int32_t K, int32_t d) {
     return probe_grad_chunks(n) * (K > 0 ? K : 0) * (int64_t(d > 0 ? d : 0) + 1);
+}
+
+#define CLANE_MIXTURE_WRAPPERS(SUF, CT, T, AT)                                                                         \
+    int clane_mixture_estep_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \
+                                  int64_t n, const AT *mean, const AT *Wm, const AT *cst, int32_t R, int32_t K,        \
+                                  int32_t flags, AT *resp, double *ll_ws, double *ll, int32_t *assign,                 \
+                                  int64_t ld_assign, void *stream) {                                                   \
+        return mixture_estep<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, mean, Wm, cst, R, K,  \
+                                    flags, resp, ll_ws, ll, assign, ld_assign, stream);                                \
+    }                                                                                                                  \
+    int clane_mixture_mstep_##SUF(const CT *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows,        \
+                                  int64_t n, const AT *mean, const AT *resp, int32_t K, AT *ws, AT *S, AT *nk,         \
+                                  void *stream) {                                                                      \
+        return mixture_mstep<T, AT>(reinterpret_cast<const T *>(Z), table_rows, d, ldz, rows, n, mean, resp, K, ws, S, \
+                                    nk, stream);                                                                       \
+    }
+CLANE_MIXTURE_WRAPPERS(f32, float, float, float)
+CLANE_MIXTURE_WRAPPERS(f64, double, double, double)
+CLANE_MIXTURE_WRAPPERS(bf16, uint16_t, bf16_t, float)
+#undef CLANE_MIXTURE_WRAPPERS
+int64_t clane_mixture_ll_ws_len(int64_t n, int32_t R) { return probe_row_tiles(n) * (R > 0 ? R : 0); }
+int64_t clane_mixture_mstep_ws_len(int64_t n, int32_t K, int32_t d) {
+    return probe_grad_chunks(n) * (K > 0 ? K : 0) * (2 * int64_t(d > 0 ? d : 0) + 1);
 }
 
 #define CLANE_KMEANS_WRAPPERS(SUF, CT, T, AT)                                                                          \

@@ -699,6 +699,54 @@ class Graph(torch.utils.data.Dataset):
             return out
         return select_clusters(ks, run) if listed else run(ks[0])
 
+    def soft_cluster(self, k=None, labels=None, vertices=None, restarts: int = 10, seed: int = 0, max_iter: int = 100,
+                     tol: float = 1e-3, reg_covar: float = 1e-6, criterion: str = "bic", table: str = "Z",
+                     return_memberships: bool = False) -> dict:
+        """Soft clusters of the CURRENT embeddings (extension, mixture.py): a diagonal-covariance Gaussian mixture fitted
+        by EM as scikit-learn's ``GaussianMixture(covariance_type="diag")`` defines it, every restart at once on the GPU
+        from the partitions of ``cluster``'s k-means, the restart of highest lower bound reported.  ``labels``,
+        ``vertices`` and ``table`` as ``cluster`` takes them; ``k`` (1..64) defaults to the number of classes.  Returns
+        ``{"table", "clustered", "clusters", "restarts", "seed", "log_likelihood" (mean per row), "lower_bound", "bic",
+        "aic", "iterations", "converged", "best_restart", "weights", "soft_sizes", "sizes", "empty", "clamped",
+        "mean_entropy" (the mean of -sum r log r / log K, 0 for K = 1), "confident" (the share of rows whose top
+        responsibility is >= 0.9)}``, with labels also ``nmi``, ``ari``, ``purity`` of the hard assignment and
+        ``class_names``; with ``return_memberships`` also ``"vertices"``, ``"assignments"``, ``"memberships"`` (float64
+        numpy [n, K]) and ``"model"`` (a ``mixture.MixtureModel`` with ``save`` / ``load`` / ``predict``).  ``k`` may be a
+        sequence of counts: every one is fitted with the same seeds, the result is that of the lowest ``criterion``
+        ("bic" / "aic", ties to the smaller count) and carries ``selection = {criterion, candidates, chosen}``.  Reads
+        the engine's table where it lies and changes no state.  Several GPUs and a column division raise
+        NotImplementedError."""
+        from .cluster import clustering_scores, contingency
+        from .mixture import CRITERIA, GaussianMixture, check_component_counts, describe_fit, select_components
+        if k is None and labels is None:
+            raise ValueError("soft_cluster: give k, the number of components, or labels whose classes it defaults to")
+        if criterion not in CRITERIA:
+            raise ValueError(f"soft_cluster: criterion must be one of {CRITERIA}, got {criterion!r}")
+        y = names = None
+        if labels is not None:
+            vertices, y, names = self._resolve_labels(labels, False, "soft_cluster")
+        elif vertices is None:
+            vertices = list(range(len(self)))
+        ks, listed = check_component_counts(len(names) if k is None else k)
+        gm = GaussianMixture(self.engine(), reg_covar=reg_covar, tol=tol, max_iter=max_iter)
+        tab, rows = gm.table_and_rows(vertices, table)
+
+        def run(k_one):
+            fit = gm.fit(tab, rows, k_one, restarts=restarts, seed=seed)
+            out = describe_fit(fit, table, restarts, seed)
+            if names is not None:
+                yt = torch.as_tensor(y, dtype=torch.int64).reshape(-1).to(tab.device)
+                nmi, ari, purity = clustering_scores(contingency(yt, fit.assign, len(names), k_one))
+                out.update({"nmi": float(nmi), "ari": float(ari), "purity": float(purity),
+                            "class_names": [str(c) for c in names]})
+            if return_memberships:
+                out["vertices"] = [int(v) for v in vertices]
+                out["assignments"] = fit.assign.tolist()
+                out["memberships"] = fit.resp.double().cpu().numpy()
+                out["model"] = fit.model(table=table)
+            return out
+        return select_components([run(int(v)) for v in ks], criterion) if listed else run(ks[0])
+
     def silhouette(self, partition=None, labels=None, vertices=None, table: str = "Z", metric: str = "euclidean",
                    max_points: Optional[int] = 65536, seed: int = 0) -> dict:
         """The exact silhouette of a partition of the CURRENT embeddings (extension; ``table="X"``: of the content):

@@ -87,7 +87,11 @@ extern "C" {
                              *    CLANE_TSNE_NN_MAX_POINTS points)
                              *    + clane_probe_predict_* (applying fitted probes: class probabilities and the top-m classes
                              *    of rows of the table under F stacked soft-max or one-vs-rest models, fused into the logits'
-                             *    contraction) */
+                             *    contraction)
+                             *    + clane_mixture_estep_*, clane_mixture_mstep_*, clane_mixture_ll_ws_len,
+                             *    clane_mixture_mstep_ws_len (soft clusters: R stacked diagonal Gaussian mixtures on centred
+                             *    rows of the table -- responsibilities, log-likelihood and arg-max fused into the logits'
+                             *    contraction, the sufficient statistics one contraction over the rows) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -768,6 +772,44 @@ int clane_probe_predict_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, i
                              const float *W, const float *bias, const int8_t *col_state, int32_t F, int32_t C,
                              int32_t top_m, int32_t flags, int32_t *top_class, float *top_prob, float *proba,
                              void *stream);
+
+/* ---- Gaussian mixtures (csrc/mixture.h) --------------------------------------------------------------------------------
+ * One EM iteration of R diagonal-covariance Gaussian mixtures of K components, 1 <= K <= CLANE_MIXTURE_MAX_COMPONENTS, on the
+ * rows `rows[0..n)` of the table Z (an index outside [0, table_rows) reads as a zero row).  Every row is centred in the
+ * loaders: xc = x - mean, mean [d] in the accumulate type (a zero row is centred like any row).  Both steps contract the
+ * 2 d wide operand phi(x) = [xc^2 | xc].  The restarts are stacked as the probes' fits are: Kp = K rounded up to a power of
+ * two, restart r's component c in row r * Kp + c (rows of pad components are ignored).
+ *
+ * estep: Wm [R * Kp, 2 d] = [-a/2 | mu a] with a = 1 / variance, cst [R * Kp] = log pi - (d log 2 pi + sum log variance +
+ *   sum mu^2 a) / 2, both in the accumulate type.  The logits l = phi . Wm^T + cst never reach memory; per (row, restart)
+ *   the log-sum-exp over the K real components gives
+ *   ll[r] = sum_i lse_i                                  (always; double; ll_ws: mixture_ll_ws_len doubles)
+ *   resp[i, r Kp + c] = exp(l_c - lse_i), pad columns 0   (CLANE_MIXTURE_WRITE_RESP; resp is [n, R * Kp] contiguous)
+ *   assign[i, r] = argmax_c, ties to the lowest component (CLANE_MIXTURE_WRITE_ASSIGN; assign is [n, ld_assign >= R])
+ * mstep: S [K, 2 d] = resp^T . phi(Z[rows]) and nk [K] = sum_i resp[i, :], K = R * Kp here, the rows in chunks whose partial
+ *   tiles are summed in chunk order (ws: mixture_mstep_ws_len elements of the accumulate type).
+ * No atomics: two calls give the same bits, and a restart's results do not depend on the other restarts of the call. */
+#define CLANE_MIXTURE_MAX_COMPONENTS 64
+#define CLANE_MIXTURE_WRITE_RESP 1
+#define CLANE_MIXTURE_WRITE_ASSIGN 2
+int clane_mixture_estep_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const float *mean, const float *Wm, const float *cst, int32_t R, int32_t K, int32_t flags,
+                            float *resp, double *ll_ws, double *ll, int32_t *assign, int64_t ld_assign, void *stream);
+int clane_mixture_estep_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const double *mean, const double *Wm, const double *cst, int32_t R, int32_t K, int32_t flags,
+                            double *resp, double *ll_ws, double *ll, int32_t *assign, int64_t ld_assign, void *stream);
+int clane_mixture_estep_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const float *mean, const float *Wm, const float *cst, int32_t R, int32_t K, int32_t flags,
+                             float *resp, double *ll_ws, double *ll, int32_t *assign, int64_t ld_assign, void *stream);
+int clane_mixture_mstep_f32(const float *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const float *mean, const float *resp, int32_t K, float *ws, float *S, float *nk, void *stream);
+int clane_mixture_mstep_f64(const double *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                            const double *mean, const double *resp, int32_t K, double *ws, double *S, double *nk,
+                            void *stream);
+int clane_mixture_mstep_bf16(const uint16_t *Z, int64_t table_rows, int32_t d, int64_t ldz, const int32_t *rows, int64_t n,
+                             const float *mean, const float *resp, int32_t K, float *ws, float *S, float *nk, void *stream);
+int64_t clane_mixture_ll_ws_len(int64_t n, int32_t R);
+int64_t clane_mixture_mstep_ws_len(int64_t n, int32_t K, int32_t d);
 
 /* ---- node clustering (csrc/kmeans.h) ----------------------------------------------------------------------------------
  * One Lloyd iteration of k-means for R restarts at once on the rows `rows[0..n)` of the table Z (an index outside
