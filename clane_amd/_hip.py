@@ -80,6 +80,21 @@ SIGNATURES["clane_spmm_update_class_tiles_f32"] = (
               _i32, _p, _p, _i64, _p])
 SIGNATURES["clane_spmm_update_owned_tiles_f32"] = (
     C.c_int, [_p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _i32, _p, _i64, _p])
+# one weight per row instead of one per edge (csrc/spmm_update.h, UNIFORM): the calls above with `row_weight` for P
+SIGNATURES["clane_row_weight_f32"] = SIGNATURES["clane_row_weight_f64"] = (C.c_int, [_p, _p, _i64, _p, _p, _p])
+SIGNATURES["clane_spmm_update_rw_f32"] = (
+    C.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i64, _i32, _p, _p])
+SIGNATURES["clane_spmm_update_tiles_rw_f32"] = SIGNATURES["clane_spmm_update_tiles_f32"]
+SIGNATURES["clane_spmm_update_class_rw_f32"] = (
+    C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _p,
+              _p, _p])
+SIGNATURES["clane_spmm_update_class_tiles_rw_f32"] = (
+    C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32,
+              _i32, _i32, _p, _p, _i64, _p])
+SIGNATURES["clane_spmm_update_owned_rw_f32"] = (
+    C.c_int, [_p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _p, _p])
+SIGNATURES["clane_spmm_update_owned_tiles_rw_f32"] = (
+    C.c_int, [_p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, C.c_float, _p, _i64, _i32, _i32, _i32, _p, _i64, _p])
 for _s in ("f32", "f64"):
     SIGNATURES[f"clane_degree_weighted_sums_{_s}"] = (C.c_int, [_p, _p, _p, _i64, _p, _p, _p])
     SIGNATURES[f"clane_edge_score_finalize_{_s}"] = (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p])
@@ -372,6 +387,12 @@ class OwnedPlan:
                 and bool((a["seg_vrow"] < a["bat_vrow_ptr"].diff()[seg_bat]).all())
         if not ok:
             raise ValueError("OwnedPlan: the arrays do not describe a plan (see include/clane_hip.h)")
+        # every segment's row (relative to the call's first row, as row_id is): what the per-row-weight calls index by
+        self.seg_row = torch.zeros(0, dtype=torch.int32, device=device)
+        if a["seg_len"].numel():
+            vrow = a["bat_vrow_ptr"][seg_bat].long() + a["seg_vrow"].long()
+            owner = torch.searchsorted(a["row_vptr"].long(), vrow, right=True) - 1
+            self.seg_row = a["row_id"][owner].contiguous().to(device)
         self.max_edge = int((a["seg_e0"] + a["seg_len"]).max()) if a["seg_len"].numel() else 0
         self.max_row = int(a["row_id"].max()) if self.n_rows else -1
         self.max_part = int(a["row_part"].max()) if self.n_rows else -1
@@ -781,6 +802,19 @@ class KernelBackend(abc.ABC):
         """spmm_update_owned for every column tile, the tile loop inside the persistent workgroups."""
         raise NotImplementedError(f"{type(self).__name__} has no spmm_update_owned_tiles")
 
+    # one weight per row instead of one per edge (csrc/spmm_update.h, UNIFORM): optional in the same way -- a backend
+    # without them keeps the per-edge calls, and SweepEngine asks `has_row_weight` before it looks at P's rows.  Every
+    # ``*_rw`` call is the call of the same name without the suffix with `row_weight` (one weight per row of the call)
+    # where that takes P; the class calls also take `item_row` (after item_slot), the owned calls read the plan's seg_row.
+    def has_row_weight(self, dtype) -> bool:
+        """Whether row_weight and the spmm_update*_rw calls exist for tables of `dtype`."""
+        return False
+
+    def row_weight(self, rowptr, P, nrows: int, w, mixed):
+        """w[r] = the first weight of row r (0 without edges); mixed[0] = 1 if a row of P holds two different bit
+        patterns, else 0."""
+        raise NotImplementedError(f"{type(self).__name__} has no row_weight")
+
     def bind(self, method: str, *args, **kwargs):
         """A zero-argument callable that makes the call ``method(*args, **kwargs)``; an implementation may
         pre-marshal it (HipKernels does)."""
@@ -1127,6 +1161,106 @@ class HipKernels(KernelBackend):
         self._invoke(self.lib.clane_spmm_update_owned_tiles_f32, "clane_spmm_update_owned_tiles",
                      _vec(colidx, torch.int32, "colidx"), _vec(P, torch.float32, "P"), C.cast(C.pointer(plan.c), _p),
                      int(block_threads), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
+                     self._spmm_flags(beyond_cache=beyond_cache, loads=loads, ahead=ahead),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
+
+    # -- one weight per row instead of one per edge --------------------------------------------------------------
+    def has_row_weight(self, dtype) -> bool:
+        return dtype == torch.float32
+
+    def row_weight(self, rowptr, P, nrows: int, w, mixed):
+        if w.dtype != P.dtype or w.numel() < nrows or rowptr.numel() < nrows + 1:
+            raise ValueError("row_weight: w must hold one weight of P's dtype per row of rowptr")
+        self._invoke(self._fn("clane_row_weight", P.dtype), "clane_row_weight", _vec(rowptr, torch.int64, "rowptr"),
+                     _vec(P, P.dtype, "P"), nrows, _vec(w, P.dtype, "w"), _vec(mixed, torch.int32, "mixed"),
+                     self._stream(P))
+
+    @staticmethod
+    def _row_weights(name: str, w, rows: int):
+        """The `row_weight` argument of a *_rw call that reads the weights of rows [0, rows)."""
+        if w.numel() < rows:
+            raise ValueError(f"{name}: row_weight holds {w.numel()} rows, the call reads {rows}")
+        return _vec(w, torch.float32, "row_weight")
+
+    def spmm_update_rw(self, rowptr, colidx, row_weight, nrows: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
+                       long_threshold: int, partials, sinks_untouched: bool = False, beyond_cache: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_rw", Z_old, X, Z_new, f32_only=True)
+        self._invoke(self.lib.clane_spmm_update_rw_f32, "clane_spmm_update_rw",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
+                     self._row_weights("spmm_update_rw", row_weight, nrows), nrows, row0, zo, ldz, xp, ldx, gamma, zn, ldo,
+                     d, long_threshold, self._spmm_flags(sinks_untouched, beyond_cache),
+                     _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+
+    def spmm_update_tiles_rw(self, rowptr, colidx, row_weight, nrows: int, row0: int, Z_old, X, gamma: float, Z_new,
+                             d: int, tile_cols: int, long_threshold: int, partials, partials_stride: int,
+                             sinks_untouched: bool = False, beyond_cache: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_tiles_rw", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, self.spmm_partials_len(nrows, 0))
+        self._invoke(self.lib.clane_spmm_update_tiles_rw_f32, "clane_spmm_update_tiles_rw",
+                     _vec(rowptr, torch.int64, "rowptr"), _vec(colidx, torch.int32, "colidx"),
+                     self._row_weights("spmm_update_tiles_rw", row_weight, nrows), nrows, row0, zo, ldz, xp, ldx, gamma,
+                     zn, ldo, d, tile_cols, long_threshold, self._spmm_flags(sinks_untouched, beyond_cache),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
+
+    def spmm_update_class_rw(self, colidx, row_weight, item_e0, item_len, item_slot, item_row, items_per_block: int,
+                             class_rows, slot_ptr, row0: int, Z_old, X, gamma: float, Z_new, d: int, slab, partials,
+                             beyond_cache: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_class_rw", Z_old, X, Z_new, f32_only=True)
+        n_blocks = self._item_blocks("spmm_update_class_rw", items_per_block, item_e0, item_len, item_slot, item_row)
+        rows = int(class_rows.max()) + 1 if class_rows.numel() else 0          # item_row holds class rows only
+        self._invoke(self.lib.clane_spmm_update_class_rw_f32, "clane_spmm_update_class_rw",
+                     _vec(colidx, torch.int32, "colidx"), self._row_weights("spmm_update_class_rw", row_weight, rows),
+                     _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
+                     _vec(item_slot, torch.int32, "item_slot"), _vec(item_row, torch.int32, "item_row"), n_blocks,
+                     items_per_block, _vec(class_rows, torch.int32, "class_rows"), _vec(slot_ptr, torch.int64, "slot_ptr"),
+                     class_rows.numel(), row0, zo, ldz, xp, ldx, gamma, zn, ldo, d,
+                     self._spmm_flags(beyond_cache=beyond_cache), _vec(slab, torch.float32, "slab"),
+                     _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+
+    def spmm_update_class_tiles_rw(self, colidx, row_weight, item_e0, item_len, item_slot, item_row, items_per_block: int,
+                                   class_rows, slot_ptr, n_slots: int, row0: int, Z_old, X, gamma: float, Z_new, d: int,
+                                   tile_cols: int, slab, partials, partials_stride: int, beyond_cache: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_class_tiles_rw", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, class_rows.numel())
+        n_blocks = self._item_blocks("spmm_update_class_tiles_rw", items_per_block, item_e0, item_len, item_slot, item_row)
+        if slab.numel() < -(-d // tile_cols) * self.spmm_class_slab_len(n_slots, tile_cols):
+            raise ValueError("spmm_update_class_tiles_rw: the slab does not hold every tile's chunk sums")
+        rows = int(class_rows.max()) + 1 if class_rows.numel() else 0
+        self._invoke(self.lib.clane_spmm_update_class_tiles_rw_f32, "clane_spmm_update_class_tiles_rw",
+                     _vec(colidx, torch.int32, "colidx"), self._row_weights("spmm_update_class_tiles_rw", row_weight, rows),
+                     _vec(item_e0, torch.int64, "item_e0"), _vec(item_len, torch.int32, "item_len"),
+                     _vec(item_slot, torch.int32, "item_slot"), _vec(item_row, torch.int32, "item_row"), n_blocks,
+                     items_per_block, _vec(class_rows, torch.int32, "class_rows"), _vec(slot_ptr, torch.int64, "slot_ptr"),
+                     class_rows.numel(), n_slots, row0, zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
+                     self._spmm_flags(beyond_cache=beyond_cache), _vec(slab, torch.float32, "slab"),
+                     _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
+
+    def spmm_update_owned_rw(self, colidx, row_weight, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X,
+                             gamma: float, Z_new, d: int, partials, beyond_cache: bool = False, loads: int = 0,
+                             ahead: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tables("spmm_update_owned_rw", Z_old, X, Z_new, f32_only=True)
+        self._owned_plan_fits("spmm_update_owned_rw", plan, d, colidx, colidx, row0, Z_old, X, Z_new, partials)
+        self._invoke(self.lib.clane_spmm_update_owned_rw_f32, "clane_spmm_update_owned_rw",
+                     _vec(colidx, torch.int32, "colidx"),
+                     self._row_weights("spmm_update_owned_rw", row_weight, plan.max_row + 1),
+                     C.cast(C.pointer(plan.c), _p), _vec(plan.seg_row, torch.int32, "seg_row"), int(block_threads), row0,
+                     zo, ldz, xp, ldx, gamma, zn, ldo, d,
+                     self._spmm_flags(beyond_cache=beyond_cache, loads=loads, ahead=ahead),
+                     _vec(partials, torch.float64, "partials"), self._stream(Z_old))
+
+    def spmm_update_owned_tiles_rw(self, colidx, row_weight, plan: OwnedPlan, block_threads: int, row0: int, Z_old, X,
+                                   gamma: float, Z_new, d: int, tile_cols: int, partials, partials_stride: int,
+                                   beyond_cache: bool = False, loads: int = 0, ahead: bool = False):
+        zo, ldz, xp, ldx, zn, ldo = self._tile_args("spmm_update_owned_tiles_rw", Z_old, X, Z_new, d, tile_cols, partials,
+                                                    partials_stride, plan.max_part + 1)
+        if not self.has_spmm_owned(torch.float32, tile_cols):
+            raise ValueError(f"spmm_update_owned_tiles_rw: no owned instance for tiles of {tile_cols} columns")
+        self._owned_plan_fits("spmm_update_owned_tiles_rw", plan, tile_cols, colidx, colidx, row0, Z_old, X, Z_new)
+        self._invoke(self.lib.clane_spmm_update_owned_tiles_rw_f32, "clane_spmm_update_owned_tiles_rw",
+                     _vec(colidx, torch.int32, "colidx"),
+                     self._row_weights("spmm_update_owned_tiles_rw", row_weight, plan.max_row + 1),
+                     C.cast(C.pointer(plan.c), _p), _vec(plan.seg_row, torch.int32, "seg_row"), int(block_threads), row0,
+                     zo, ldz, xp, ldx, gamma, zn, ldo, d, tile_cols,
                      self._spmm_flags(beyond_cache=beyond_cache, loads=loads, ahead=ahead),
                      _vec(partials, torch.float64, "partials"), partials_stride, self._stream(Z_old))
 

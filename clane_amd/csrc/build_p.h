@@ -347,6 +347,37 @@ __global__ __launch_bounds__(kBlock) void edge_score_finalize_kernel(
     }
 }
 
+// Rows whose weights are all the SAME float.  In reference mode the scores share one global denominator
+// (similarity.py:37), so on a graph of a few million edges they are all O(1e-9), their exp is exactly 1 and the soft-max
+// (graph.py:126) leaves P[e] == 1 / deg bit for bit on every row -- K3 can then read one weight per row instead of one per
+// edge (spmm_update.h, UNIFORM).  A workgroup on `rows_per_block` consecutive rows: w[r] = the row's first weight (0 for
+// a row without edges), and mixed[0] |= 1 if any edge of any row differs from its row's first in a single BIT (an integer
+// atomic: the answer is a set, not a sum).  The caller zeroes mixed[0] before the launch.
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+template <typename A>
+__global__ __launch_bounds__(kBlock) void row_weight_kernel(const int64_t *__restrict__ rowptr, const A *__restrict__ P,
+                                                            int64_t nrows, A *__restrict__ w, int32_t *__restrict__ mixed,
+                                                            int rows_per_block) {
+    // One wave per row (config 3: 262 us per build_P; what else was tried is in profiles/r21_uniform_weights.md).
+    const int wave = threadIdx.x / kWave, lane = lane_id();
+    const int64_t row_begin = int64_t(blockIdx.x) * rows_per_block;
+    const int64_t row_end = row_begin + rows_per_block < nrows ? row_begin + rows_per_block : nrows;
+    bool differs = false;
+    for (int64_t r = row_begin + wave; r < row_end; r += kWavesPerBlock) {
+        const int64_t e0 = rowptr[r], e1 = rowptr[r + 1];
+        A first = A(0);
+        if (e1 > e0) {
+            first = P[e0];
+#pragma unroll 8
+            for (int64_t e = e0 + lane; e < e1; e += kWave) differs |= !same_bits(P[e], first);
+        }
+        if (lane == 0) w[r] = first;
+    }
+    if (__any(differs) && lane == 0) atomicOr(mixed, 1);
+}
+
 // out[w] = XCD that workgroup w of this launch ran on (diagnostic: see xcc_id()).
 __global__ void xcc_ids_kernel(int32_t *__restrict__ out) {
     if (threadIdx.x == 0) out[blockIdx.x] = xcc_id();

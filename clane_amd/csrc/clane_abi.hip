@@ -397,6 +397,20 @@ int edge_score_finalize(const int64_t *rowptr, const int32_t *colidx, int64_t nr
     return check_launch("edge_score_finalize");
 }
 
+// One weight per row where build_P left a row uniform (build_p.h, row_weight_kernel); mixed[0] = 0 before, |= 1 by the kernel.
+template <typename A>
+int row_weights(const int64_t *rowptr, const A *P, int64_t nrows, A *w, int32_t *mixed, void *stream) {
+    REQUIRE(nrows >= 0, "row_weight: bad shape nrows=%lld", (long long)nrows);
+    REQUIRE(mixed, "row_weight: null mixed");
+    const hipError_t e = hipMemsetAsync(mixed, 0, sizeof(int32_t), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CLANE_ERR_LAUNCH, "row_weight: %s", hipGetErrorString(e));
+    if (nrows == 0) return CLANE_OK;
+    REQUIRE(rowptr && P && w, "row_weight: null pointer");
+    row_weight_kernel<A><<<row_grid(nrows), kBlock, 0, (hipStream_t)stream>>>(rowptr, P, nrows, w, mixed,
+                                                                             rows_per_block(nrows));
+    return check_launch("row_weight");
+}
+
 inline int64_t spmm_main_grid(int64_t nrows) { return row_grid(nrows); }
 
 // Column tiles of a pass: tile t covers columns [t * cols, min(d, (t + 1) * cols)).  Each pass has ONE launcher, and the
@@ -422,18 +436,21 @@ bool tiles_share_layout(int d, int tile_cols) {
             and_text " (d=%d tile_cols=%d)", what, d, (tiles).cols)
 
 // The row pass's kernel entries, per tile and fused: one sub-wave per row for the short rows of narrow matrices
-template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED, bool UNIFORM>
 constexpr auto row_kernel() {
-    if constexpr (LPR < kWave && VEC > 1) return &spmm_update_subrow_kernel<T, PT, VEC, LPR, U, MIRRORED>;
-    else return &spmm_update_kernel<T, PT, VEC, LPR, U, MIRRORED>;
+    if constexpr (LPR < kWave && VEC > 1) return &spmm_update_subrow_kernel<T, PT, VEC, LPR, U, MIRRORED, UNIFORM>;
+    else return &spmm_update_kernel<T, PT, VEC, LPR, U, MIRRORED, UNIFORM>;
 }
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM>
 constexpr auto row_tiles_kernel() {
-    if constexpr (LPR < kWave) return &spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, U>;
-    else return &spmm_update_tiles_kernel<T, PT, VEC, LPR, U>;
+    if constexpr (LPR < kWave) return &spmm_update_subrow_tiles_kernel<T, PT, VEC, LPR, U, UNIFORM>;
+    else return &spmm_update_tiles_kernel<T, PT, VEC, LPR, U, UNIFORM>;
 }
 
-template <typename T, typename PT, bool FUSED>
+// UNIFORM, in the three K3 launchers that take it (the *_rw_f32 entry points): `P` holds one weight per ROW of the call
+// (clane_row_weight_* found every row of P uniform), the kernels are the UNIFORM instances of spmm_update.h, there is no
+// mirror.  Everything else -- checks, instance choice, grids -- is the per-edge call's, which is what keeps the two bit for bit.
+template <typename T, typename PT, bool FUSED, bool UNIFORM = false>
 int spmm_update_impl(const char *what, const int64_t *rowptr, const int32_t *colidx, const PT *P, int64_t nrows,
                      int64_t row0, const Tables<T> &t, Tiles tiles, int64_t long_threshold, int32_t flags,
                      double *delta_partials, void *stream) {
@@ -442,6 +459,7 @@ int spmm_update_impl(const char *what, const int64_t *rowptr, const int32_t *col
             (long long)row0, d);
     if constexpr (FUSED) REQUIRE_TILES(T, d, tiles, what, true, "");
     REQUIRE(t.mirror_complete(), "%s: incomplete mirror descriptor", what);
+    if constexpr (UNIFORM) REQUIRE(t.mirror == nullptr, "%s: no mirror with per-row weights", what);
     REQUIRE(t.wide_enough(), "%s: leading dimension < d", what);
     REQUIRE(long_threshold >= 0, "%s: negative long_threshold", what);
     REQUIRE(delta_partials, "%s: null delta_partials", what);
@@ -466,11 +484,13 @@ int spmm_update_impl(const char *what, const int64_t *rowptr, const int32_t *col
                                                                  rows_per_block(nrows), how..., delta_partials);
             };
             if constexpr (FUSED) {
-                if constexpr (VEC > 1) go(row_tiles_kernel<T, PT, VEC, LPR, U>(), beyond, tg);
+                if constexpr (VEC > 1) go(row_tiles_kernel<T, PT, VEC, LPR, U, UNIFORM>(), beyond, tg);
+            } else if constexpr (UNIFORM) {
+                go(row_kernel<T, PT, VEC, LPR, U, false, true>(), mir, beyond);
             } else if (mir.row_ptr != nullptr) {   // the mirrored instances prefetch a row's places (spmm_update.h)
-                go(row_kernel<T, PT, VEC, LPR, U, true>(), mir, beyond);
+                go(row_kernel<T, PT, VEC, LPR, U, true, false>(), mir, beyond);
             } else {
-                go(row_kernel<T, PT, VEC, LPR, U, false>(), mir, beyond);
+                go(row_kernel<T, PT, VEC, LPR, U, false, false>(), mir, beyond);
             }
         };
         // two fp32 rows per instruction (512-byte rows: the column tiles, config 2, the N = 2 column slices): with the
@@ -547,12 +567,14 @@ int spmm_update_split(const int64_t *rowptr, const int32_t *colidx, const PT *P,
 
 // The class pass over column tiles: chunk sums into the slab (tile t's at slab + t * n_slots * ld_slab, all tiles' at
 // the same time), then the fixed-order combine + epilogue.  The per-tile call has no use for n_slots and passes 0.
-template <typename T, typename PT, bool FUSED>
+// UNIFORM: see spmm_update_impl; `item_row` (every item's row, relative to the call's first row) is then required.
+template <typename T, typename PT, bool FUSED, bool UNIFORM = false>
 int spmm_update_class_impl(const char *what, const int32_t *colidx, const PT *P, const int64_t *item_e0,
                            const int32_t *item_len, const int32_t *item_slot, int64_t n_blocks, int32_t items_per_block,
                            const int32_t *class_rows, const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots,
                            int64_t row0, const Tables<T> &t, Tiles tiles, int32_t flags,
-                           typename Elem<T>::acc_t *slab, double *delta_partials, void *stream) {
+                           typename Elem<T>::acc_t *slab, double *delta_partials, void *stream,
+                           const int32_t *item_row = nullptr) {
     const int32_t d = t.d;
     constexpr int kPad = FUSED ? 8 : 1;      // fused: block 8 j + b of every tile on XCD class b, so the count is rounded up
     REQUIRE(t.mirror_complete(), "%s: incomplete mirror descriptor", what);
@@ -567,6 +589,7 @@ int spmm_update_class_impl(const char *what, const int32_t *colidx, const PT *P,
     if (n_rows == 0) return CLANE_OK;
     REQUIRE(colidx && P && item_e0 && item_len && item_slot && class_rows && slot_ptr && t.present() && slab &&
                 delta_partials, "%s: null pointer", what);
+    if constexpr (UNIFORM) REQUIRE(item_row && t.mirror == nullptr, "%s: per-row weights need item_row and no mirror", what);
     REQUIRE(!t.aliased(), "%s: Z_new must not alias Z_old", what);
     REQUIRE(aligned16(slab), "%s: slab must be 16-byte aligned", what);
     const Layout L = t.layout(tiles.cols);
@@ -588,12 +611,12 @@ int spmm_update_class_impl(const char *what, const int32_t *colidx, const PT *P,
         const unsigned combine_grid = unsigned(n_tiles) * unsigned(combine_blocks);
         auto chunks = [&]<int CU>() {
             if constexpr (!FUSED)
-                spmm_class_chunk_kernel<T, PT, VEC, LPR, CU><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
-                    colidx, P, item_e0, item_len, item_slot, items_per_block, t.Z_old, t.ldz, d, slab, ld_slab);
+                spmm_class_chunk_kernel<T, PT, VEC, LPR, CU, UNIFORM><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
+                    colidx, P, item_e0, item_len, item_slot, items_per_block, t.Z_old, t.ldz, d, slab, ld_slab, item_row);
             else if constexpr (VEC > 1)
-                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, CU><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
+                spmm_class_chunk_tiles_kernel<T, PT, VEC, LPR, CU, UNIFORM><<<chunk_grid, kBlock, 0, (hipStream_t)stream>>>(
                     colidx, P, item_e0, item_len, item_slot, int(n_blocks), items_per_block, t.Z_old, t.ldz, d, slab,
-                    ld_slab, slab_stride, TileGrid{chunk_blocks, tiles.cols, 0});
+                    ld_slab, slab_stride, TileGrid{chunk_blocks, tiles.cols, 0}, item_row);
         };
         if (n_blocks > 0 && kDeepU > 0 && beyond) chunks.template operator()<(kDeepU > 0 ? kDeepU : U)>();
         else if (n_blocks > 0) chunks.template operator()<U>();
@@ -616,10 +639,11 @@ constexpr int64_t kLdsDefaultLimit = 64 * 1024;
 
 // The owned class pass over the column tiles of a table t.d wide.  Its kernel has one entry for both forms, so there is
 // no FUSED here; everything but the tiles themselves is reported as spmm_update_owned, whichever entry point was called.
-template <typename T, typename PT>
+// UNIFORM: see spmm_update_impl; `seg_row` (every segment's row, relative to the call's first row) is then required.
+template <typename T, typename PT, bool UNIFORM = false>
 int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P, const clane_owned_plan_t *plan,
                            int32_t block_threads, int64_t row0, const Tables<T> &t, Tiles tiles, bool fused, int32_t flags,
-                           double *delta_partials, void *stream) {
+                           double *delta_partials, void *stream, const int32_t *seg_row = nullptr) {
     using A = typename Elem<T>::acc_t;
     const int32_t d = tiles.cols;          // what the instance and the LDS sums are sized by: one full tile
     if (fused) REQUIRE_TILES(T, t.d, tiles, what, tiles.part_stride >= 0, ", the partials' stride >= 0");
@@ -637,6 +661,7 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
                 plan->seg_e0 && plan->seg_len && plan->seg_vrow && plan->row_id && plan->row_part && plan->row_vptr &&
                 t.present() && delta_partials,
             "spmm_update_owned: null pointer");
+    if constexpr (UNIFORM) REQUIRE(seg_row, "spmm_update_owned: per-row weights need seg_row");
     REQUIRE(!t.aliased(), "spmm_update_owned: Z_new must not alias Z_old");
     const Layout L = t.layout(d);
     REQUIRE(L.vec && (L.lpr == 32 || L.lpr == 64) && d <= L.lpr * Elem<T>::kVec,
@@ -650,7 +675,7 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
     const bool beyond = (flags & CLANE_SPMM_TABLE_BEYOND_CACHE) != 0;
     int rc = CLANE_OK;
     auto launch = [&]<int VEC, int LPR, int U>() {
-        auto *kernel = spmm_owned_kernel<T, PT, VEC, LPR, U>;
+        auto *kernel = spmm_owned_kernel<T, PT, VEC, LPR, U, UNIFORM>;
         if (lds > kLdsDefaultLimit) {      // above the default per-workgroup limit: ask for it, once per size
             static int64_t granted = 0;
             if (lds > granted) {
@@ -666,7 +691,7 @@ int spmm_update_owned_impl(const char *what, const int32_t *colidx, const PT *P,
         }
         kernel<<<unsigned(plan->n_groups), unsigned(block_threads), size_t(lds), (hipStream_t)stream>>>(
             colidx, P, op, row0, t.Z_old, t.ldz, t.X, t.ldx, t.gamma, t.Z_new, t.ldo, t.d, tiles.cols, tiles.part_stride,
-            (flags & CLANE_OWNED_EPILOGUE_AHEAD) != 0, beyond, delta_partials);
+            (flags & CLANE_OWNED_EPILOGUE_AHEAD) != 0, beyond, delta_partials, seg_row);
     };
     constexpr int KV = Elem<T>::kVec;
     // Row loads in flight per wave.  Asked for through CLANE_OWNED_LOADS(n) (the instances: 6, 8, 12 at two rows per
@@ -1698,6 +1723,74 @@ int clane_spmm_update_owned_tiles_f32(const int32_t *colidx, const float *P, con
                                                 TABLES(float), Tiles{tile_cols, partials_tile_stride}, true, flags,
                                                 delta_partials, stream);
 }
+// ---- one weight per row instead of one per edge (csrc/spmm_update.h, UNIFORM): float only, no mirror ----------------
+int clane_row_weight_f32(const int64_t *rowptr, const float *P, int64_t nrows, float *row_weight, int32_t *mixed,
+                         void *stream) {
+    return row_weights<float>(rowptr, P, nrows, row_weight, mixed, stream);
+}
+int clane_row_weight_f64(const int64_t *rowptr, const double *P, int64_t nrows, double *row_weight, int32_t *mixed,
+                         void *stream) {
+    return row_weights<double>(rowptr, P, nrows, row_weight, mixed, stream);
+}
+int clane_spmm_update_rw_f32(const int64_t *rowptr, const int32_t *colidx, const float *row_weight, int64_t nrows,
+                             int64_t row0, const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                             float *Z_new, int64_t ldo, int32_t d, int64_t long_threshold, int32_t flags,
+                             double *delta_partials, void *stream) {
+    return spmm_update_impl<float, float, false, true>("spmm_update_rw", rowptr, colidx, row_weight, nrows, row0,
+                                                       TABLES(float), Tiles{d, 0}, long_threshold, flags, delta_partials,
+                                                       stream);
+}
+int clane_spmm_update_tiles_rw_f32(const int64_t *rowptr, const int32_t *colidx, const float *row_weight, int64_t nrows,
+                                   int64_t row0, const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                                   float *Z_new, int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold,
+                                   int32_t flags, double *delta_partials, int64_t partials_tile_stride, void *stream) {
+    return spmm_update_impl<float, float, true, true>("spmm_update_tiles_rw", rowptr, colidx, row_weight, nrows, row0,
+                                                      TABLES(float), Tiles{tile_cols, partials_tile_stride}, long_threshold,
+                                                      flags, delta_partials, stream);
+}
+int clane_spmm_update_class_rw_f32(const int32_t *colidx, const float *row_weight, const int64_t *item_e0,
+                                   const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                   int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                   const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const float *Z_old, int64_t ldz,
+                                   const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                   int32_t flags, float *slab, double *delta_partials, void *stream) {
+    return spmm_update_class_impl<float, float, false, true>("spmm_update_class_rw", colidx, row_weight, item_e0, item_len,
+                                                             item_slot, n_blocks, items_per_block, class_rows, slot_ptr,
+                                                             n_rows, 0, row0, TABLES(float), Tiles{d, 0}, flags, slab,
+                                                             delta_partials, stream, item_row);
+}
+int clane_spmm_update_class_tiles_rw_f32(const int32_t *colidx, const float *row_weight, const int64_t *item_e0,
+                                         const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                         int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                         const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots, int64_t row0,
+                                         const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                                         float *Z_new, int64_t ldo, int32_t d, int32_t tile_cols, int32_t flags,
+                                         float *slab, double *delta_partials, int64_t partials_tile_stride,
+                                         void *stream) {
+    return spmm_update_class_impl<float, float, true, true>("spmm_update_class_tiles_rw", colidx, row_weight, item_e0,
+                                                            item_len, item_slot, n_blocks, items_per_block, class_rows,
+                                                            slot_ptr, n_rows, n_slots, row0, TABLES(float),
+                                                            Tiles{tile_cols, partials_tile_stride}, flags, slab,
+                                                            delta_partials, stream, item_row);
+}
+int clane_spmm_update_owned_rw_f32(const int32_t *colidx, const float *row_weight, const clane_owned_plan_t *plan,
+                                   const int32_t *seg_row, int32_t block_threads, int64_t row0, const float *Z_old,
+                                   int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo,
+                                   int32_t d, int32_t flags, double *delta_partials, void *stream) {
+    return spmm_update_owned_impl<float, float, true>("spmm_update_owned_rw", colidx, row_weight, plan, block_threads, row0,
+                                                      TABLES(float), Tiles{d, 0}, false, flags, delta_partials, stream,
+                                                      seg_row);
+}
+int clane_spmm_update_owned_tiles_rw_f32(const int32_t *colidx, const float *row_weight, const clane_owned_plan_t *plan,
+                                         const int32_t *seg_row, int32_t block_threads, int64_t row0, const float *Z_old,
+                                         int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo,
+                                         int32_t d, int32_t tile_cols, int32_t flags, double *delta_partials,
+                                         int64_t partials_tile_stride, void *stream) {
+    return spmm_update_owned_impl<float, float, true>("spmm_update_owned_tiles_rw", colidx, row_weight, plan, block_threads,
+                                                      row0, TABLES(float), Tiles{tile_cols, partials_tile_stride}, true,
+                                                      flags, delta_partials, stream, seg_row);
+}
+
 int64_t clane_spmm_class_slab_len(int64_t n_slots, int32_t d) { return n_slots * (ceil_div(d, 8) * 8); }
 int64_t clane_spmm_split_slab_len(int64_t n_segments, int32_t d) { return n_segments * (ceil_div(d, 8) * 8); }
 

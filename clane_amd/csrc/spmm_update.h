@@ -57,13 +57,20 @@ struct EdgeChunk {
     A p;
 };
 
-template <typename A, typename PT>
+// UNIFORM (here and in everything below that takes it): the launch's rows each have ONE weight -- build_P left every row of
+// P with the same float on all of its edges (in reference mode at scale: 1 / deg, see row_weight_kernel in build_p.h) --
+// and `P` is then that weight PER ROW of the call, w[row], not per edge.  A chunk is colidx alone, the weight is fetched
+// once where the row / item / segment is claimed and feeds the same fma per edge in the same order: bit for bit the
+// per-edge instance, without the per-edge stream (4 bytes per edge and column tile), its broadcast and its register.
+// Every caller passes the weight `w` (no default: a UNIFORM caller that forgot it would sum zeros); the per-edge
+// instances do not read it.
+template <typename A, typename PT, bool UNIFORM = false>
 __device__ __forceinline__ EdgeChunk<A> load_chunk(const int32_t *__restrict__ colidx, const PT *__restrict__ P,
                                                    int64_t e, int64_t e1) {
     EdgeChunk<A> ch{0, A(0)};
     if (e + lane_id() < e1) {
         ch.c = colidx[e + lane_id()];
-        ch.p = A(P[e + lane_id()]);
+        if constexpr (!UNIFORM) ch.p = A(P[e + lane_id()]);
     }
     return ch;
 }
@@ -75,10 +82,11 @@ __device__ __forceinline__ EdgeChunk<A> load_chunk(const int32_t *__restrict__ c
 //    block and waits for every load on its own (seen in the .s), so there every load is
 //    unconditional from an always-valid address (edge past the end -> the chunk's first column,
 //    column lane past d -> column 0) and the VALUE is zeroed instead.
-template <typename T, int VEC, int LPR, int U>
+template <typename T, int VEC, int LPR, int U, bool UNIFORM = false>
 __device__ __forceinline__ void accumulate_chunk(const EdgeChunk<typename Elem<T>::acc_t> &ch, int n,
                                                  const T *__restrict__ zcol, int64_t ldz, bool col_ok,
-                                                 typename Elem<T>::acc_t (&acc)[VEC]) {
+                                                 typename Elem<T>::acc_t (&acc)[VEC],
+                                                 [[maybe_unused]] typename Elem<T>::acc_t w) {
     using A = typename Elem<T>::acc_t;
     constexpr int EPW = kWave / LPR;  // neighbour rows fetched by one wave-instruction
     constexpr bool kBranchFree = sizeof(T) == 2;
@@ -95,10 +103,12 @@ __device__ __forceinline__ void accumulate_chunk(const EdgeChunk<typename Elem<T
             A pv;
             if constexpr (LPR == kWave) {
                 cj = lane_get_uniform(c_all, idx & (kWave - 1));
-                pv = lane_get_uniform(ch.p, idx & (kWave - 1));
+                if constexpr (UNIFORM) pv = w;
+                else pv = lane_get_uniform(ch.p, idx & (kWave - 1));
             } else {
                 cj = lane_get(c_all, idx & (kWave - 1));
-                pv = lane_get(ch.p, idx & (kWave - 1));
+                if constexpr (UNIFORM) pv = w;
+                else pv = lane_get(ch.p, idx & (kWave - 1));
             }
             const bool in_row = idx < n;
             pj[u] = in_row ? pv : A(0);
@@ -123,18 +133,19 @@ __device__ __forceinline__ void accumulate_chunk(const EdgeChunk<typename Elem<T
 
 // acc[k] += sum over edges e in [e0, e1) of P[e] * Z[colidx[e], col + k].  `first` holds the
 // chunk starting at e0 if `have_first` (prefetched by the caller).  Called by all 64 lanes.
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __device__ __forceinline__ void gather_accumulate(const int32_t *__restrict__ colidx, const PT *__restrict__ P,
                                                   int64_t e0, int64_t e1, const T *__restrict__ zcol, int64_t ldz,
                                                   bool col_ok, typename Elem<T>::acc_t (&acc)[VEC],
-                                                  const EdgeChunk<typename Elem<T>::acc_t> &first, bool have_first) {
+                                                  const EdgeChunk<typename Elem<T>::acc_t> &first, bool have_first,
+                                                  [[maybe_unused]] typename Elem<T>::acc_t w) {
     using A = typename Elem<T>::acc_t;
     for (int64_t e = e0; e < e1; e += kWave) {
         const int64_t left = e1 - e;
         const int n = left < kWave ? int(left) : kWave;
         EdgeChunk<A> ch = first;
-        if (!(have_first && e == e0)) ch = load_chunk<A, PT>(colidx, P, e, e1);
-        accumulate_chunk<T, VEC, LPR, U>(ch, n, zcol, ldz, col_ok, acc);
+        if (!(have_first && e == e0)) ch = load_chunk<A, PT, UNIFORM>(colidx, P, e, e1);
+        accumulate_chunk<T, VEC, LPR, U, UNIFORM>(ch, n, zcol, ldz, col_ok, acc, w);
     }
 }
 
@@ -251,7 +262,7 @@ __device__ __forceinline__ void mirror_store_prefetched(const Mirror<T> &mirror,
 // registers (the bf16 sub-wave instance would drop from 5 to 4 waves per SIMD) that a one-GPU sweep must not pay.
 // The work of ONE workgroup of the row pass: rows [block * rows_per_block, ...) of the call, the block's delta partial to
 // *partial.  spmm_update_kernel runs it per blockIdx.x; spmm_update_tiles_kernel runs it per (column tile, block).
-template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED, bool UNIFORM = false>
 __device__ __forceinline__ void spmm_update_block(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
@@ -307,10 +318,12 @@ __device__ __forceinline__ void spmm_update_block(
     int64_t e0 = 0, e1 = 0, m0 = 0, m1 = 0;
     int32_t places = 0;
     EdgeChunk<A> ch{0, A(0)};
+    [[maybe_unused]] A w = A(0);            // UNIFORM: the claimed row's weight, requested with its first chunk
     if (cur < nb) {
         e0 = s_rowptr[cur];
         e1 = s_rowptr[cur + 1];
-        ch = load_chunk<A, PT>(colidx, P, e0, e1);
+        ch = load_chunk<A, PT, UNIFORM>(colidx, P, e0, e1);
+        if constexpr (UNIFORM) w = A(P[row_begin + cur]);
         places = places_of(cur, m0, m1);
     }
     while (cur < nb) {
@@ -318,12 +331,14 @@ __device__ __forceinline__ void spmm_update_block(
         int64_t n0 = 0, n1 = 0, mn0 = 0, mn1 = 0;
         int32_t places_n = 0;
         EdgeChunk<A> chn{0, A(0)};
+        [[maybe_unused]] A wn = A(0);
         if (nxt < nb) {
             n0 = s_rowptr[nxt];
             n1 = s_rowptr[nxt + 1];
 #if CLANE_SPMM_PREFETCH
-            chn = load_chunk<A, PT>(colidx, P, n0, n1);
+            chn = load_chunk<A, PT, UNIFORM>(colidx, P, n0, n1);
 #endif
+            if constexpr (UNIFORM) wn = A(P[row_begin + nxt]);
             places_n = places_of(nxt, mn0, mn1);
         }
         if (!(long_threshold > 0 && e1 - e0 > long_threshold) && !(skip_sinks && e1 == e0)) {
@@ -341,7 +356,8 @@ __device__ __forceinline__ void spmm_update_block(
                 A acc[VEC];
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = A(0);
-                gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, e0, e1, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, ch, true);
+                gather_accumulate<T, PT, VEC, LPR, U, UNIFORM>(colidx, P, e0, e1, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, ch,
+                                                               true, w);
                 fold_subwaves<LPR>(acc);
                 Pack<T, VEC> out{};
                 if (writer) rsum += finish_pack<T, VEC>(x, zo, acc, gamma, e1 > e0, Znew + r * ldo + c0, out, nt_store);
@@ -357,10 +373,11 @@ __device__ __forceinline__ void spmm_update_block(
         m0 = mn0;
         m1 = mn1;
         places = places_n;
+        if constexpr (UNIFORM) w = wn;
 #if CLANE_SPMM_PREFETCH
         ch = chn;
 #else
-        if (cur < nb) ch = load_chunk<A, PT>(colidx, P, e0, e1);
+        if (cur < nb) ch = load_chunk<A, PT, UNIFORM>(colidx, P, e0, e1);
 #endif
     }
     // No closing barrier: a wave that runs out of rows leaves (its slot goes to another workgroup);
@@ -372,15 +389,15 @@ __device__ __forceinline__ void spmm_update_block(
     if (lane == 0) *partial = dsum;
 }
 
-template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED, bool UNIFORM = false>
 __global__ CLANE_SPMM_BOUNDS void spmm_update_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
     typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
     bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
-    spmm_update_block<T, PT, VEC, LPR, U, MIRRORED>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma, Znew, ldo, d,
-                                                    long_threshold, skip_sinks, rows_per_block, mirror, nt_store,
-                                                    blockIdx.x, partials + blockIdx.x);
+    spmm_update_block<T, PT, VEC, LPR, U, MIRRORED, UNIFORM>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma, Znew,
+                                                             ldo, d, long_threshold, skip_sinks, rows_per_block, mirror,
+                                                             nt_store, blockIdx.x, partials + blockIdx.x);
 }
 
 // ---- every COLUMN TILE of a pass in one launch ---------------------------------------------------------------------
@@ -400,7 +417,7 @@ struct TileGrid {
     }
 };
 
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __global__ CLANE_SPMM_BOUNDS void spmm_update_tiles_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
@@ -409,10 +426,10 @@ __global__ CLANE_SPMM_BOUNDS void spmm_update_tiles_kernel(
     const int tile = tg.tile();
     const int block = int(blockIdx.x) - tile * tg.per_tile;
     const int c = tile * tg.tile_cols;
-    spmm_update_block<T, PT, VEC, LPR, U, false>(rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma,
-                                                 Znew + c, ldo, tg.width(tile, d), long_threshold, skip_sinks,
-                                                 rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store, block,
-                                                 partials + tile * tg.part_stride + block);
+    spmm_update_block<T, PT, VEC, LPR, U, false, UNIFORM>(rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma,
+                                                          Znew + c, ldo, tg.width(tile, d), long_threshold, skip_sinks,
+                                                          rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0},
+                                                          nt_store, block, partials + tile * tg.part_stride + block);
 }
 
 // Rows that need fewer than 64 lanes (LPR < 64; e.g. d=128 bf16: 16 lanes x 16 B, or the column slices of a
@@ -434,7 +451,7 @@ __global__ CLANE_SPMM_BOUNDS void spmm_update_tiles_kernel(
 #else
 #define CLANE_SUBROW_BOUNDS __launch_bounds__(kBlock)
 #endif
-template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED, bool UNIFORM = false>
 __device__ __forceinline__ void spmm_update_subrow_block(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
@@ -478,7 +495,7 @@ __device__ __forceinline__ void spmm_update_subrow_block(
     int64_t e_end = 0;
     int nbuf = 0, pos = 0;     // buffered edges (one per lane: c, p) and how many of them are consumed
     int c = 0;
-    A p = A(0);
+    A p = A(0);                // UNIFORM: the open row's one weight (uniform over the sub-wave), not a buffered edge's
     [[maybe_unused]] int64_t m0 = 0, m1 = 0;   // the open row's mirror places: range in mirror.slot, the first LPR of
     [[maybe_unused]] int32_t places = 0;       // them one per lane, requested when the row is claimed
     Pack<T, VEC> x{}, zo{};
@@ -519,6 +536,7 @@ __device__ __forceinline__ void spmm_update_subrow_block(
                     }
                     e_next = e0;
                     e_end = e0 + dg;
+                    if constexpr (UNIFORM) p = A(P[r]);
                     if constexpr (MIRRORED) {
                         m0 = s_mptr[mine];
                         m1 = s_mptr[mine + 1];
@@ -537,13 +555,13 @@ __device__ __forceinline__ void spmm_update_subrow_block(
             pos = 0;
             nbuf = 0;
             c = 0;
-            p = A(0);
+            if constexpr (!UNIFORM) p = A(0);
             if (!done) {                     // refill: the next LPR edges of the row, one per lane
                 const int64_t left = e_end - e_next;
                 nbuf = left < LPR ? int(left) : LPR;
                 if (sl < nbuf) {
                     c = colidx[e_next + sl];
-                    p = A(P[e_next + sl]);
+                    if constexpr (!UNIFORM) p = A(P[e_next + sl]);
                 }
                 e_next += nbuf;
             }
@@ -557,7 +575,8 @@ __device__ __forceinline__ void spmm_update_subrow_block(
             // pos is a multiple of U and below LPR while a row is open; lanes past nbuf hold c = 0, p = 0
             const int src = sub_base + ((pos + u) & (LPR - 1));
             const int cj = lane_get(c, src);
-            pj[u] = lane_get(p, src);
+            if constexpr (UNIFORM) pj[u] = pos + u < nbuf ? p : A(0);      // what the lanes past nbuf hold per edge: 0
+            else pj[u] = lane_get(p, src);
             z[u] = load_pack<T, VEC>(Zold + int64_t(cj) * ldz + c0s);
         }
 #pragma unroll
@@ -578,19 +597,20 @@ __device__ __forceinline__ void spmm_update_subrow_block(
     if (lane == 0) *partial = dsum;
 }
 
-template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED>
+template <typename T, typename PT, int VEC, int LPR, int U, bool MIRRORED, bool UNIFORM = false>
 __global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
     typename Elem<T>::acc_t gamma, T *__restrict__ Znew, int64_t ldo, int d, int64_t long_threshold,
     bool skip_sinks, int rows_per_block, Mirror<T> mirror, bool nt_store, double *__restrict__ partials) {
-    spmm_update_subrow_block<T, PT, VEC, LPR, U, MIRRORED>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma, Znew,
-                                                           ldo, d, long_threshold, skip_sinks, rows_per_block, mirror,
-                                                           nt_store, blockIdx.x, partials + blockIdx.x);
+    spmm_update_subrow_block<T, PT, VEC, LPR, U, MIRRORED, UNIFORM>(rowptr, colidx, P, nrows, row0, Zold, ldz, X, ldx, gamma,
+                                                                    Znew, ldo, d, long_threshold, skip_sinks,
+                                                                    rows_per_block, mirror, nt_store, blockIdx.x,
+                                                                    partials + blockIdx.x);
 }
 
 // Every column tile of the sub-wave row pass in one launch (see spmm_update_tiles_kernel).
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_tiles_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const PT *__restrict__ P, int64_t nrows,
     int64_t row0, const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx,
@@ -599,10 +619,10 @@ __global__ CLANE_SUBROW_BOUNDS void spmm_update_subrow_tiles_kernel(
     const int tile = tg.tile();
     const int block = int(blockIdx.x) - tile * tg.per_tile;
     const int c = tile * tg.tile_cols;
-    spmm_update_subrow_block<T, PT, VEC, LPR, U, false>(rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma,
-                                                        Znew + c, ldo, tg.width(tile, d), long_threshold, skip_sinks,
-                                                        rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store,
-                                                        block, partials + tile * tg.part_stride + block);
+    spmm_update_subrow_block<T, PT, VEC, LPR, U, false, UNIFORM>(
+        rowptr, colidx, P, nrows, row0, Zold + c, ldz, X + c, ldx, gamma, Znew + c, ldo, tg.width(tile, d), long_threshold,
+        skip_sinks, rows_per_block, Mirror<T>{nullptr, nullptr, nullptr, 0}, nt_store, block,
+        partials + tile * tg.part_stride + block);
 }
 
 // One workgroup of WAVES waves per long row.  Wave w gathers the 64-aligned edge slice w; slices are
@@ -645,7 +665,7 @@ __global__ __launch_bounds__(WAVES *kWave) void spmm_long_kernel(
         A acc[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = A(0);
-        gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, a, b, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, none, false);
+        gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, a, b, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, none, false, A(0));
         fold_subwaves<LPR>(acc);
         if (wave > 0) {
 #pragma unroll
@@ -710,7 +730,7 @@ __global__ __launch_bounds__(WAVES *kWave) void spmm_split_segment_kernel(
         A acc[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = A(0);
-        gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, a, b, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, none, false);
+        gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, a, b, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, none, false, A(0));
         fold_subwaves<LPR>(acc);
         if (wave > 0) {
 #pragma unroll
@@ -782,16 +802,19 @@ __device__ __forceinline__ Pack<A, VEC> slab_load(const A *p) {
     }
 }
 
-template <typename T, typename PT, int VEC, int LPR, int U>
+// UNIFORM: `item_row` (the row of every item, relative to the call's first row; unused otherwise) says whose weight in P
+// an item takes.
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __device__ __forceinline__ void spmm_class_chunk_block(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
     const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int items_per_block,
     const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab,
-    int64_t block) {
+    int64_t block, [[maybe_unused]] const int32_t *__restrict__ item_row = nullptr) {
     using A = typename Elem<T>::acc_t;
     __shared__ int64_t s_e0[kMaxItemsPerBlock];
     __shared__ int s_len[kMaxItemsPerBlock];
     __shared__ int s_slot[kMaxItemsPerBlock];
+    __shared__ int s_row[UNIFORM ? kMaxItemsPerBlock : 1];
     __shared__ int s_next;
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -802,6 +825,7 @@ __device__ __forceinline__ void spmm_class_chunk_block(
         s_e0[i] = item_e0[base + i];
         s_len[i] = item_len[base + i];
         s_slot[i] = item_slot[base + i];
+        if constexpr (UNIFORM) s_row[i] = item_row[base + i];
     }
     if (threadIdx.x == 0) s_next = kWavesPerBlock;
     __syncthreads();
@@ -814,19 +838,23 @@ __device__ __forceinline__ void spmm_class_chunk_block(
     int cur = wave;
     int64_t e0 = 0, e1 = 0;
     EdgeChunk<A> ch{0, A(0)};
+    [[maybe_unused]] A w = A(0);            // UNIFORM: the weight of the item's row (padding items, length 0: none)
     if (cur < items_per_block) {
         e0 = s_e0[cur];
         e1 = e0 + s_len[cur];
-        ch = load_chunk<A, PT>(colidx, P, e0, e1);
+        ch = load_chunk<A, PT, UNIFORM>(colidx, P, e0, e1);
+        if constexpr (UNIFORM) w = e1 > e0 ? A(P[s_row[cur]]) : A(0);
     }
     while (cur < items_per_block) {
         const int nxt = claim();
         int64_t n0 = 0, n1 = 0;
         EdgeChunk<A> chn{0, A(0)};
+        [[maybe_unused]] A wn = A(0);
         if (nxt < items_per_block) {
             n0 = s_e0[nxt];
             n1 = n0 + s_len[nxt];
-            chn = load_chunk<A, PT>(colidx, P, n0, n1);
+            chn = load_chunk<A, PT, UNIFORM>(colidx, P, n0, n1);
+            if constexpr (UNIFORM) wn = n1 > n0 ? A(P[s_row[nxt]]) : A(0);
         }
         if (e1 > e0) {
             A *out = slab + int64_t(s_slot[cur]) * ld_slab;
@@ -836,7 +864,8 @@ __device__ __forceinline__ void spmm_class_chunk_block(
                 A acc[VEC];
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = A(0);
-                gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, e0, e1, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc, ch, true);
+                gather_accumulate<T, PT, VEC, LPR, U, UNIFORM>(colidx, P, e0, e1, Zold + (col_ok ? c0 : 0), ldz, col_ok, acc,
+                                                               ch, true, w);
                 fold_subwaves<LPR>(acc);
                 if (col_ok && sub == 0) {
                     Pack<A, VEC> o;
@@ -850,33 +879,35 @@ __device__ __forceinline__ void spmm_class_chunk_block(
         e0 = n0;
         e1 = n1;
         ch = chn;
+        if constexpr (UNIFORM) w = wn;
     }
 }
 
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __global__ __launch_bounds__(kBlock) void spmm_class_chunk_kernel(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
     const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int items_per_block,
-    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab) {
-    spmm_class_chunk_block<T, PT, VEC, LPR, U>(colidx, P, item_e0, item_len, item_slot, items_per_block, Zold, ldz, d,
-                                               slab, ld_slab, blockIdx.x);
+    const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab,
+    const int32_t *__restrict__ item_row) {
+    spmm_class_chunk_block<T, PT, VEC, LPR, U, UNIFORM>(colidx, P, item_e0, item_len, item_slot, items_per_block, Zold, ldz,
+                                                        d, slab, ld_slab, blockIdx.x, item_row);
 }
 
 // Every column tile's chunks in one launch (see spmm_update_tiles_kernel).  tg.per_tile is the item-block count rounded
 // UP to a multiple of 8, so block 8 j + b of every tile still runs on XCD class b; the workgroups of the padding
 // (block >= n_blocks) return at once.  Tile t's chunk sums live at slab + t * slab_stride: all tiles' at the same time.
-template <typename T, typename PT, int VEC, int LPR, int U>
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __global__ __launch_bounds__(kBlock) void spmm_class_chunk_tiles_kernel(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, const int64_t *__restrict__ item_e0,
     const int32_t *__restrict__ item_len, const int32_t *__restrict__ item_slot, int n_blocks, int items_per_block,
     const T *__restrict__ Zold, int64_t ldz, int d, typename Elem<T>::acc_t *__restrict__ slab, int64_t ld_slab,
-    int64_t slab_stride, TileGrid tg) {
+    int64_t slab_stride, TileGrid tg, const int32_t *__restrict__ item_row) {
     const int tile = tg.tile();
     const int block = int(blockIdx.x) - tile * tg.per_tile;
     if (block >= n_blocks) return;                           // uniform over the workgroup, before any barrier
-    spmm_class_chunk_block<T, PT, VEC, LPR, U>(colidx, P, item_e0, item_len, item_slot, items_per_block,
-                                               Zold + tile * tg.tile_cols, ldz, tg.width(tile, d),
-                                               slab + tile * slab_stride, ld_slab, block);
+    spmm_class_chunk_block<T, PT, VEC, LPR, U, UNIFORM>(colidx, P, item_e0, item_len, item_slot, items_per_block,
+                                                        Zold + tile * tg.tile_cols, ldz, tg.width(tile, d),
+                                                        slab + tile * slab_stride, ld_slab, block, item_row);
 }
 
 // One workgroup of kCombineWaves waves per class row.  Wave w adds the w-th contiguous share of the row's slots IN ORDER;
@@ -1035,12 +1066,14 @@ struct OwnedPlan {
     int chunk;
 };
 
-template <typename T, typename PT, int VEC, int LPR, int U>
+// UNIFORM: `seg_row` (per segment: its row relative to the call's first row; unused otherwise) says whose weight in P a
+// segment takes.
+template <typename T, typename PT, int VEC, int LPR, int U, bool UNIFORM = false>
 __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
     const int32_t *__restrict__ colidx, const PT *__restrict__ P, OwnedPlan plan, int64_t row0,
     const T *__restrict__ Zold, int64_t ldz, const T *__restrict__ X, int64_t ldx, typename Elem<T>::acc_t gamma,
     T *__restrict__ Znew, int64_t ldo, int d_left, int tile_cols, int64_t part_stride, bool ahead, bool nt_store,
-    double *__restrict__ partials) {
+    double *__restrict__ partials, [[maybe_unused]] const int32_t *__restrict__ seg_row) {
     using A = typename Elem<T>::acc_t;
     constexpr int W = LPR * VEC;            // elements of one LDS sum: the whole tile row (the host checks tile_cols <= W)
     constexpr int kRows = kWave / LPR;      // rows finished by one wave at a time
@@ -1082,22 +1115,26 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
             int64_t e0 = 0, e1 = 0;
             int vr = 0;
             EdgeChunk<A> ch{0, A(0)};
+            [[maybe_unused]] A w = A(0);    // UNIFORM: the weight of the segment's row
             if (cur < n) {
                 e0 = plan.seg_e0[sa + cur];
                 e1 = e0 + plan.seg_len[sa + cur];
                 vr = plan.seg_vrow[sa + cur];
-                ch = load_chunk<A, PT>(colidx, P, e0, e0 + chunk < e1 ? e0 + chunk : e1);
+                ch = load_chunk<A, PT, UNIFORM>(colidx, P, e0, e0 + chunk < e1 ? e0 + chunk : e1);
+                if constexpr (UNIFORM) w = A(P[seg_row[sa + cur]]);
             }
             while (cur < n) {
                 const int nxt = claim();
                 int64_t n0 = 0, n1 = 0;
                 int vn = 0;
                 EdgeChunk<A> chn{0, A(0)};
+                [[maybe_unused]] A wn = A(0);
                 if (nxt < n) {
                     n0 = plan.seg_e0[sa + nxt];
                     n1 = n0 + plan.seg_len[sa + nxt];
                     vn = plan.seg_vrow[sa + nxt];
-                    chn = load_chunk<A, PT>(colidx, P, n0, n0 + chunk < n1 ? n0 + chunk : n1);
+                    chn = load_chunk<A, PT, UNIFORM>(colidx, P, n0, n0 + chunk < n1 ? n0 + chunk : n1);
+                    if constexpr (UNIFORM) wn = A(P[seg_row[sa + nxt]]);
                 }
                 A *sum = s_sum + vr * W + c0;
                 for (int64_t p = e0; p < e1; p += chunk) {   // the segment's pieces, in order
@@ -1105,7 +1142,7 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
                     A acc[VEC];
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[k] = A(0);
-                    gather_accumulate<T, PT, VEC, LPR, U>(colidx, P, p, pe, zcol, ldz, col_ok, acc, ch, p == e0);
+                    gather_accumulate<T, PT, VEC, LPR, U, UNIFORM>(colidx, P, p, pe, zcol, ldz, col_ok, acc, ch, p == e0, w);
                     fold_subwaves<LPR>(acc);
                     if (col_ok && sub == 0) {
                         Pack<A, VEC> t = load_pack<A, VEC>(sum);
@@ -1119,6 +1156,7 @@ __global__ __launch_bounds__(kOwnedMaxBlock) void spmm_owned_kernel(
                 e1 = n1;
                 vr = vn;
                 ch = chn;
+                if constexpr (UNIFORM) w = wn;
             }
             __syncthreads();                                  // the step is done in this workgroup
         }

@@ -71,6 +71,11 @@ class DiagnosticsMixin:
         total = self.E_total * (d * s + 8) + self.V * 3 * d * s
         return total / max(self.world, 1) / 8e12
 
+    def _sweeps_read_row_weights(self) -> bool:
+        if getattr(self, "uniform_weights", False) is False or not getattr(self, "P_valid", False):
+            return False
+        return self._uniform if self._uniform is not None else self._resolve_uniform()
+
     def kernel_config(self) -> dict:
         """Everything that decides which K3 kernels a sweep launches over which rows, and with which compile-time
         tuning: measurements of a kernel (profiles/traffic.json) are only valid for the configuration they were
@@ -101,6 +106,9 @@ class DiagnosticsMixin:
                 **({"fused_tiles": sorted(self.fused_tiles)} if getattr(self, "fused_tiles", None) else {}),
                 **({"owned_ahead": True} if getattr(self, "class_owned", False) and getattr(self, "owned_ahead", False)
                    else {}),
+                # only where the sweeps of the current P read one weight per row (spmm_update*_rw); asked of the rows of P
+                # here when no sweep has asked yet
+                **({"uniform_weights": True} if self._sweeps_read_row_weights() else {}),
                 }
 
     def exchange_bytes_per_sweep(self) -> int:

@@ -31,7 +31,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _hip, fused, owned, xcd
+from . import _hip, fused, owned, uniform, xcd
 from .blocks import BlockRows, ClassItems, PartialLayout, SplitRows
 from .comm import TorchComm
 from .diagnostics import DiagnosticsMixin
@@ -70,7 +70,8 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                  owned_max_edges: int = xcd.OWNED_MAX_EDGES, owned_row_edges: int = xcd.OWNED_ROW_EDGES,
                  owned_groups: int = xcd.OWNED_GROUPS, owned_lds_bytes: int = xcd.OWNED_LDS_BYTES,
                  owned_block_threads: int = xcd.OWNED_BLOCK_THREADS, owned_chunk: Optional[int] = None,
-                 owned_loads: int = xcd.OWNED_LOADS, owned_ahead: Optional[bool] = None, fused_tiles=None):
+                 owned_loads: int = xcd.OWNED_LOADS, owned_ahead: Optional[bool] = None, fused_tiles=None,
+                 uniform_weights=None):
         """``exchange`` (N > 1 only) -- how the sweep is divided over the GPUs:
         "auto" (default) -- "columns" while a rank's slice of a row is >= 64 bytes, else "halo" (pick_exchange).
         "columns" -- every GPU holds the whole graph and d/N COLUMNS of X and Z.  ``Z[:, c] = X[:, c] + gamma P Z[:, c]``
@@ -96,6 +97,15 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         ("row", "class", "owned").  Taken only with more than one tile, uniform tiles (tile t is columns
         [t x width, (t + 1) x width)), fp32 tables, no mirrors and a backend that has the calls; every other engine
         keeps the per-tile plan.  Bit for bit the same either way.
+        ``uniform_weights`` -- where every row of P holds ONE float on all of its edges (reference mode on a graph of
+        millions of edges leaves 1 / deg: every score is O(1e-9) and its exp exactly 1), the row, class and owned passes
+        read that weight once per row instead of once per edge and column tile (spmm_update*_rw; long / split rows and
+        mirrored launches keep the per-edge calls).  "auto" = whenever the rows of P are found uniform (one pass over P
+        and 4 bytes read back before the first sweep on every new P); True = the same, and a P
+        that is not uniform is an error; False = never; None = xcd.UNIFORM_WEIGHTS_DEFAULT for a table far beyond the
+        Infinity Cache (`beyond_cache`), False for every other (a P that turns out mixed pays the look for nothing: config
+        2's build_P + first sweep 0.46 -> 0.67 ms).  Taken only on one GPU with
+        fp32 tables and a backend that has the calls.  Bit for bit the same either way.
         The constructor is a sequence of steps, each a method: the division over the ranks, the class-pass thresholds,
         the row layout, the row bins, the structure upload, the launch lists, the exchange lists, the tables, scratch."""
         if X.dim() != 2 or X.shape[0] != csr.num_vertices:
@@ -122,6 +132,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         ahead = xcd.OWNED_EPILOGUE_AHEAD if owned_ahead is None else bool(owned_ahead)
         self.owned_ahead = bool(ahead and self.k.owned_epilogue_ahead)
         self._choose_fused_tiles(fused_tiles)
+        self._choose_uniform(uniform_weights)
         self._build_layout(csr, chunks, shuffle, seed, hot_rows_first)
         self._choose_row_bins(long_threshold, hub_threshold)
         deg = self._upload_structure()
@@ -267,8 +278,8 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         """Which passes run all column tiles in one launch: `fused_possible`, and `fused_tiles`, a frozenset of FUSED_PASSES
         (empty wherever the fused calls do not apply: the engine then keeps one launch per tile)."""
         w = self.tiles[0][1] - self.tiles[0][0]
-        uniform = all(c0 == t * w and c1 == c0 + w for t, (c0, c1) in enumerate(self.tiles))     # the cuts are even or not
-        self.fused_possible = bool(len(self.tiles) > 1 and uniform and self.world == 1 and not self._forced
+        even = all(c0 == t * w and c1 == c0 + w for t, (c0, c1) in enumerate(self.tiles))        # the cuts are even or not
+        self.fused_possible = bool(len(self.tiles) > 1 and even and self.world == 1 and not self._forced
                                    and self.dtype == torch.float32
                                    and fused.backend_has(self, w))
         if asked is None:
@@ -280,6 +291,44 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
             if any(p not in self.FUSED_PASSES for p in want):
                 raise ValueError(f"fused_tiles: passes are {self.FUSED_PASSES}, got {asked!r}")
         self.fused_tiles = frozenset(want) if self.fused_possible else frozenset()
+
+    def _choose_uniform(self, asked) -> None:
+        """`uniform_weights`: False, "auto" or True (see the constructor); `_uniform`: what the rows of the current P were
+        found to be -- None until a sweep asks (`_resolve_uniform`)."""
+        if asked is None:       # where it was measured to pay: a table far beyond the Infinity Cache (xcd.py)
+            asked = xcd.UNIFORM_WEIGHTS_DEFAULT if self.beyond_cache else False
+        if asked not in (False, True, "auto"):
+            raise ValueError(f"uniform_weights must be None, True, False or 'auto', got {asked!r}")
+        self.uniform_possible = uniform.possible(self)
+        if asked is True and not self.uniform_possible:
+            raise ValueError("uniform_weights=True: one GPU, fp32 tables and a backend with the per-row-weight calls only")
+        self.uniform_weights = asked if self.uniform_possible else False
+        self._uniform = None
+
+    def set_uniform_weights(self, asked) -> None:
+        """Switch ``uniform_weights`` between sweeps: for A/B timings on ONE engine's tables (tools/uniform_weights_ab.py)."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self._choose_uniform(asked)
+
+    # P_valid is set by everything that has just written P (build_P, build_P_bilinear, the plug-in similarities of
+    # Graph.build_P, and the tools and tests that fill eng.P themselves).  Setting it launches nothing: it only forgets
+    # what was known about the rows of the P before (`_uniform = None`), so that the next sweep looks again.  A write to
+    # P that is not followed by an assignment to P_valid leaves `row_w` and `_uniform` describing the old P.
+    @property
+    def P_valid(self) -> bool:
+        return self._P_valid
+
+    @P_valid.setter
+    def P_valid(self, ok: bool) -> None:
+        self._P_valid = bool(ok)
+        self._uniform = None
+
+    def _resolve_uniform(self) -> bool:
+        """Whether the next sweeps read one weight per row (uniform.resolve): the rows of P are looked at and the answer
+        read back, once per P."""
+        self._uniform = uniform.resolve(self)
+        return self._uniform
 
     def set_fused_tiles(self, on, ahead: Optional[bool] = None) -> None:
         """Switch the fused launches (True / False / passes by name, as the constructor's ``fused_tiles``) and the owned
@@ -837,11 +886,12 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
     def _bind(self, method: str, *args, **kwargs):
         return self.k.bind(method, *args, **kwargs)              # HipKernels: the pre-marshalled ABI call
 
-    def _build_plan(self, cur: int, dst: int, tick: int, gamma: float):
+    def _build_plan(self, cur: int, dst: int, tick: int, gamma: float, per_row: bool = False):
         """Launch lists of one sweep reading Zbuf[cur] and writing Zbuf[dst]: per block, bound kernel calls, event
         marks and the exchange; then the final reduction (into delta slot `tick`).  Everything that can be computed once (views, pointers, offsets,
         the stream each call goes to) is, so the per-sweep host cost is a few microseconds per launch -- it
-        matters at 8 GPUs, where a sweep is ~1 ms of GPU time."""
+        matters at 8 GPUs, where a sweep is ~1 ms of GPU time.  `per_row`: the row, class and owned passes read
+        `row_w` (one weight per row) instead of P."""
         Zold, Znew = self.Zbuf[cur], self.Zbuf[dst]
         per_block = []
         partial_off = self.partial_off
@@ -852,6 +902,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 rp, Xb, Zn = self.rowptr[b.local_start:], self.X_loc[self._rows(b)], self._zrows(Znew, b)
                 po, lay = partial_off[i], rows.partials
                 mir = self.mirrors_p2p[dst][i] if self.p2p else self.mirrors[i]
+                w = self.row_w[b.local_start:] if per_row else None            # uniform_possible: never with a mirror
                 # biggest rows first: split hubs, 16-wave rows, (4-wave rows), then the one-(sub-)wave-per-row pass
                 steps.append(("event", i, 0))
                 if self.d == 0:              # column-split rank without columns: nothing to launch, delta stays 0
@@ -887,9 +938,9 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 own, split = rows.owned, rows.split
                 klass = rows.klass if own is None else own.rest
                 own_all, own_t = over_tiles("owned", own, lay.klass, lambda v, p: owned.bind_launch(
-                    self, own.plan, b.row0, v, gamma, p))
+                    self, own.plan, b.row0, v, gamma, p, w))
                 class_all, class_t = over_tiles("class", klass, lay.klass, lambda v, p: fused.bind_class(
-                    self, klass, b.row0, v, gamma, slab, p, mir))
+                    self, klass, b.row0, v, gamma, slab, p, mir, w))
                 _, split_t = over_tiles(None, split, lay.split, lambda v, p: self._bind(
                     "spmm_update_split", rp, self.colidx, self.P, split.rows, split.seg_ptr, split.seg_row,
                     self.segment_edges, b.row0, v.Zold, v.X, gamma, v.Znew, v.d, slab, p, mirror=mir))
@@ -904,7 +955,7 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
                 steps += long_rows(rows.mid, 4, lay.mid)
                 steps.append(("event", i, 2))
                 row_all, row_t = over_tiles("row", b, lay.main, lambda v, p: fused.bind_row(
-                    self, rp, b.nrows, b.row0, v, gamma, p, mir))
+                    self, rp, b.nrows, b.row0, v, gamma, p, mir, w))
                 steps += sum(row_t, row_all)
                 steps.append(("event", i, 3))
                 if b.span is not None:
@@ -941,10 +992,11 @@ class SweepEngine(StagingMixin, DiagnosticsMixin):
         if self._delta_stream is not None and self._delta_busy[parity]:
             torch.cuda.current_stream(self.device).wait_event(self._delta_ev[parity])   # its last all-reduce has read delta_pp[parity]
             self._delta_busy[parity] = False
-        key = (src, dst, parity, float(gamma), stream)
+        per_row = self._uniform if self._uniform is not None else self._resolve_uniform()
+        key = (src, dst, parity, float(gamma), stream, per_row)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self._build_plan(src, dst, parity, float(gamma))
+            plan = self._plans[key] = self._build_plan(src, dst, parity, float(gamma), per_row)
         events = None
         if self.time_kernels and len(self.kernel_events) < self.MAX_TIMED_SWEEPS * len(self.blocks):
             events = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in self.blocks]

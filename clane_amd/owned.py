@@ -46,11 +46,11 @@ def plan_block(eng, layout: PartialLayout, rows_c: np.ndarray, rows_abs: np.ndar
     return OwnedRows(eng.k.make_owned_plan(plan, eng.owned_chunk, dev), rest, n_rest)
 
 
-def bind_launch(eng, plan, row0: int, v, gamma: float, partials):
+def bind_launch(eng, plan, row0: int, v, gamma: float, partials, w=None):
     """The owned launch of one block on `v` (a fused.Tables: one column tile, or all of them in one launch), bound like
     every other call of a sweep's plan.  `ahead=True` where the engine has the epilogue's look-ahead on -- only backends
-    that declare ``owned_epilogue_ahead`` are ever asked for it."""
+    that declare ``owned_epilogue_ahead`` are ever asked for it.  `w`: the weights of the block's rows (fused.py)."""
     ahead = {"ahead": True} if getattr(eng, "owned_ahead", False) else {}
-    return eng._bind(v.method("spmm_update_owned"), eng.colidx, eng.P, plan, eng.owned_block_threads, row0, v.Zold, v.X,
-                     gamma, v.Znew, v.d, *v.cols, partials, *v.strides, beyond_cache=eng.beyond_cache,
-                     loads=eng.owned_loads, **ahead)
+    return eng._bind(v.method("spmm_update_owned", w), eng.colidx, eng.P if w is None else w, plan,
+                     eng.owned_block_threads, row0, v.Zold, v.X, gamma, v.Znew, v.d, *v.cols, partials, *v.strides,
+                     beyond_cache=eng.beyond_cache, loads=eng.owned_loads, **ahead)

@@ -242,6 +242,13 @@ OWNED_DEFAULT = True
 # rows' x / z_old ahead.  Bit for bit the per-tile plan; each piece is on where its own pass's time fell by more than
 # the box's spread (profiles/r16_fused_tiles.md), else off.
 FUSED_TILES_DEFAULT = ("row", "class", "owned")
+# SweepEngine(uniform_weights=None) for a table far beyond the Infinity Cache (every other engine: False).  False = every
+# K3 call reads one weight per edge; "auto" = where build_P left every row of P with one float on all of its edges
+# (reference mode on a graph of tens of millions of edges: 1 / deg), the row, class and owned passes read one weight per
+# row instead (spmm_update*_rw, bit for bit the same).  Config 3: 3.490 -> 3.439 ms per sweep against the parent commit,
+# for 0.20 ms more per build_P.  Config 2 (4M edges, a cache-resident table) has a mixed P: the look at its rows would cost
+# 0.21 ms per build_P -- one of its sweeps -- and gain nothing (profiles/r21_uniform_weights.md).
+UNIFORM_WEIGHTS_DEFAULT = "auto"
 OWNED_EPILOGUE_AHEAD = True
 
 

@@ -91,7 +91,10 @@ extern "C" {
                              *    + clane_mixture_estep_*, clane_mixture_mstep_*, clane_mixture_ll_ws_len,
                              *    clane_mixture_mstep_ws_len (soft clusters: R stacked diagonal Gaussian mixtures on centred
                              *    rows of the table -- responsibilities, log-likelihood and arg-max fused into the logits'
-                             *    contraction, the sufficient statistics one contraction over the rows) */
+                             *    contraction, the sufficient statistics one contraction over the rows)
+                             *    + clane_row_weight_*, clane_spmm_update_rw_f32, clane_spmm_update_class_rw_f32,
+                             *    clane_spmm_update_owned_rw_f32 and their *_tiles_rw_f32 forms (K3 with one weight per row
+                             *    instead of one per edge where every row of P is uniform: bit for bit the per-edge calls) */
 
 #define CLANE_OK 0
 #define CLANE_ERR_INVALID_ARGUMENT (-1)
@@ -458,6 +461,56 @@ int clane_spmm_update_owned_tiles_f32(const int32_t *colidx, const float *P, con
                                       const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
                                       int32_t tile_cols, int32_t flags, double *delta_partials,
                                       int64_t partials_tile_stride, void *stream);
+
+/*  ONE WEIGHT PER ROW.  In reference mode the scores share one global denominator (similarity.py:37); on a graph of a few
+ *  million edges every score is O(1e-9), its exp is exactly 1 and build_P (graph.py:118-128) leaves P[e] == 1 / deg, bit for
+ *  bit, on every edge of every row.  Reading that weight per edge is then 4 bytes per edge and column tile for nothing.
+ *   clane_row_weight_*   row_weight[r] = P[rowptr[r]] (0 for a row without edges) for the nrows rows of rowptr, and
+ *                        mixed[0] = 1 if some edge's weight differs from its row's first in any bit, else 0.  To be run
+ *                        after everything that writes P; one pass over P.
+ *   clane_spmm_update_rw_f32, _class_rw_f32, _owned_rw_f32 and their _tiles_ forms
+ *                        the calls of the same names without `_rw`, for a P of which clane_row_weight_* said mixed[0] == 0:
+ *                        they take `row_weight` (one float per row of the call: rowptr's rows; for the class and owned
+ *                        calls the rows that class_rows / plan->row_id are relative to) where those take P, and read no
+ *                        per-edge weight.  The class calls also take item_row (every item's row, as
+ *                        clane_edge_score_class_* takes it), the owned calls seg_row (every segment's row, in the order
+ *                        of plan->seg_e0).  No mirror.  Z_new and every delta partial are bit for bit those of the
+ *                        per-edge call on the P the weights were taken from: the same fma per edge in the same order. */
+int clane_row_weight_f32(const int64_t *rowptr, const float *P, int64_t nrows, float *row_weight, int32_t *mixed,
+                         void *stream);
+int clane_row_weight_f64(const int64_t *rowptr, const double *P, int64_t nrows, double *row_weight, int32_t *mixed,
+                         void *stream);
+int clane_spmm_update_rw_f32(const int64_t *rowptr, const int32_t *colidx, const float *row_weight, int64_t nrows,
+                             int64_t row0, const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                             float *Z_new, int64_t ldo, int32_t d, int64_t long_threshold, int32_t flags,
+                             double *delta_partials, void *stream);
+int clane_spmm_update_tiles_rw_f32(const int64_t *rowptr, const int32_t *colidx, const float *row_weight, int64_t nrows,
+                                   int64_t row0, const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                                   float *Z_new, int64_t ldo, int32_t d, int32_t tile_cols, int64_t long_threshold,
+                                   int32_t flags, double *delta_partials, int64_t partials_tile_stride, void *stream);
+int clane_spmm_update_class_rw_f32(const int32_t *colidx, const float *row_weight, const int64_t *item_e0,
+                                   const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                   int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                   const int64_t *slot_ptr, int64_t n_rows, int64_t row0, const float *Z_old, int64_t ldz,
+                                   const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo, int32_t d,
+                                   int32_t flags, float *slab, double *delta_partials, void *stream);
+int clane_spmm_update_class_tiles_rw_f32(const int32_t *colidx, const float *row_weight, const int64_t *item_e0,
+                                         const int32_t *item_len, const int32_t *item_slot, const int32_t *item_row,
+                                         int64_t n_blocks, int32_t items_per_block, const int32_t *class_rows,
+                                         const int64_t *slot_ptr, int64_t n_rows, int64_t n_slots, int64_t row0,
+                                         const float *Z_old, int64_t ldz, const float *X, int64_t ldx, float gamma,
+                                         float *Z_new, int64_t ldo, int32_t d, int32_t tile_cols, int32_t flags,
+                                         float *slab, double *delta_partials, int64_t partials_tile_stride,
+                                         void *stream);
+int clane_spmm_update_owned_rw_f32(const int32_t *colidx, const float *row_weight, const clane_owned_plan_t *plan,
+                                   const int32_t *seg_row, int32_t block_threads, int64_t row0, const float *Z_old,
+                                   int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo,
+                                   int32_t d, int32_t flags, double *delta_partials, void *stream);
+int clane_spmm_update_owned_tiles_rw_f32(const int32_t *colidx, const float *row_weight, const clane_owned_plan_t *plan,
+                                         const int32_t *seg_row, int32_t block_threads, int64_t row0, const float *Z_old,
+                                         int64_t ldz, const float *X, int64_t ldx, float gamma, float *Z_new, int64_t ldo,
+                                         int32_t d, int32_t tile_cols, int32_t flags, double *delta_partials,
+                                         int64_t partials_tile_stride, void *stream);
 
 /* out[0] = sum of partials[0..n) in a fixed order (bitwise reproducible).  Finishes embedder.py:94 / :60.
  * ws: clane_reduce_ws_len() doubles. */
