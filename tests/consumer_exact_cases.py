@@ -25,6 +25,12 @@ third table, which only the launch taken back had written), set_Z with other dat
 ``set_Z(eng.get_Z())``: the same layout, kernels and table bits, so a difference means the wrong table, stale norms or a
 stale projection was read.
 
+The consumers that merged later -- the silhouette, ContentPCA on a table, the k-NN search, t-SNE, LabelProbe.predict, the
+Gaussian mixture and the kept label and mixture models -- live in tests/consumer_later_cases.py: A.8 holds them to a
+LAYOUT-FREE result (a plain [V, d] tensor no engine made, rows = the vertex list itself) under the plans that change what
+a consumer sees, and ``run_current_table`` compares them with the fresh engine after every step of B as well, through
+objects and models made before any sweep and through new ones (on the HIP kernels: the CPU double has none of theirs).
+
 Nothing here has a tolerance."""
 import functools
 import math
@@ -551,10 +557,14 @@ def _other_results(eng, W, init, K):
     return out
 
 
-def run_current_table(kernels, dev, run, hooks=None):
+def run_current_table(kernels, dev, run, hooks=None, later=None):
     """The `Checks` of B for run = (data, plan, cosine mode): data "sequence" is the fp64 sequence_case (exact: the
-    gathered table is also held to SequenceCase.Z), "f32" / "bf16" random float data at d = 64."""
+    gathered table is also held to SequenceCase.Z), "f32" / "bf16" random float data at d = 64.  ``later``: whether the
+    consumers of tests/consumer_later_cases.py are compared as well (None: on the HIP kernels; the CPU double has none of
+    their kernels).  ``checks.cur_seen`` lists ``eng.cur`` at every comparison."""
+    from . import consumer_later_cases as CL
     hooks = hooks or Hooks()
+    later = torch.device(dev).type == "cuda" if later is None else later
     data, plan_name, mode = run
     checks = X.Checks(f"current table {current_id(run)}")
     exact = data == "sequence"
@@ -570,10 +580,17 @@ def run_current_table(kernels, dev, run, hooks=None):
         assert len(eng.blocks) == 3 and eng.cosine_mode == mode
         hooks.after_engine(eng)
         old = _rankers(eng, W, hooks)                                     # before any sweep
+        old_later = CL.Later(eng, c.dtype, c.d) if later else None        # objects and kept models, before any sweep
+        checks.cur_seen = []
 
         def compare(step, expect=None):
+            checks.cur_seen.append(eng.cur)
             fresh = X.make_engine(kernels, dev, c, **settings)
             fresh.set_Z(eng.get_Z())
+            if later:
+                want_later = old_later.results(fresh)
+                for age, objs in (("old", old_later.old), ("new", None)):
+                    CL.record_all(checks, f"B after {step}: {age}", old_later.results(eng, objs), want_later)
             want = {f"{n} ranker {k}": v for n, r in _rankers(fresh, W, Hooks()).items()
                     for k, v in _ranker_results(r, sources, src, dst).items()}
             want_other = _other_results(fresh, W, init, fc.K)
@@ -617,4 +634,11 @@ def run_current_table(kernels, dev, run, hooks=None):
 
 
 def check_current_table(kernels, dev, run):
-    run_current_table(kernels, dev, run).assert_none_failed()
+    checks = run_current_table(kernels, dev, run)
+    checks.assert_none_failed()
+    if torch.device(dev).type == "cuda":                                  # the later consumers were compared as well
+        for step in STEPS:
+            for what in ("old silhouette-euclidean samples", "new pca Y", "old mixture resp", "new predict-softmax proba",
+                         "old label-model proba", "new mixture-model proba") + (("old knn7 ids",) * (run[0] != "sequence")):
+                assert f"B after {step}: {what}" in checks.names, (step, what)
+        assert ("B after sweep 1: new knn7 ids" in checks.names) == (run[0] != "sequence")

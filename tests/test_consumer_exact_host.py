@@ -12,7 +12,9 @@ norm 0 per edge, scores 0) and its slab ranges, and search the exclusion CSR the
 that an unsorted row is missed here as it would be there.  ``pair_labels`` bisects as well.
 
 A.7 (plan independence of the dense kernels' bits) is a statement about the HIP kernels; here it only runs to prove that
-its fixtures build."""
+its fixtures build.  So is A.8 (tests/consumer_later_cases.py): here its fixtures' teeth are asserted on the engines the
+double builds -- the vertex list, the permutation of the listed rows, the padding rows, the leading dimension, the
+three tables B passes through -- with no kernel of the later consumers involved."""
 import pytest
 import torch
 
@@ -23,6 +25,7 @@ from clane_amd import train as train_mod
 from clane_amd.plan import _round_up
 
 from . import consumer_exact_cases as CX
+from . import consumer_later_cases as CL
 from . import engine_exact_cases as X
 from .exact_cases import F32, F64
 from .test_cluster_host import KMeansOracleKernels
@@ -419,3 +422,88 @@ def test_unmutated_current_table_makes_every_comparison(k):
         for what in ("old cosine ranker top_k ids", "new bilinear ranker rank_pairs score", "project_table N",
                      "table_and_rows", "kmeans inertia", "table_and_rows gathers the exact table"):
             assert f"B after {step}: {what}" in checks.names
+
+
+# ---- the later consumers' fixtures (A.8, B) ------------------------------------------------------------------------------------
+def test_later_vertex_list_is_neither_sorted_nor_everyone():
+    L = CL.vertex_list()
+    V = X.n_vertices(X.graph())
+    assert L.numel() == CL.N_LISTED < V and L.unique().numel() == L.numel() and L.dtype == torch.int64
+    assert int(L.min()) == 0 and int(L.max()) == V - 1 and set(CL.EDGE_VERTICES) <= set(L.tolist())
+    ups = int((L[1:] > L[:-1]).sum())
+    assert L.numel() // 3 < ups < 2 * L.numel() // 3                      # neither ascending nor descending
+    for case in [c for c, _ in CL.LATER_RUNS] + [(F64, 32)]:
+        c = CL.later_case(*case)
+        assert c.part.numel() == c.Y0.shape[0] == c.resp0.shape[1] == L.numel() and torch.equal(c.vertices, L)
+        assert bool((c.resp0.sum(2) - 1).abs().max() < 1e-12) and c.has_distances == (case[0] != F64)
+
+
+def _edge_vertices(eng):
+    """The real vertices on both sides of every block edge, in table-row order."""
+    lv, out = eng.local.vertex, []
+    for b in eng.blocks[1:]:
+        lo, hi = b.local_start - 1, b.local_start
+        while lv[lo] < 0:
+            lo -= 1
+        while lv[hi] < 0:
+            hi += 1
+        out += [int(lv[lo]), int(lv[hi])]
+    return out
+
+
+@pytest.mark.parametrize("run", CL.LATER_RUNS, ids=X.plan_id)
+def test_later_fixture_has_teeth_under_plan(k, run):
+    """What each plan of A.8 changes for a consumer.  The permutation: every plan but chunks3_vertex_order (whose pos is the
+    identity) -- defaults, contiguous_tables and the tile plans through hot_rows_first.  Padding rows: the three-block
+    plans.  A leading dimension wider than d: NOT the tile plans as such (a tile is a column range of one table; ld == d
+    at d = 128, 64, 300), only PADDED_CASES."""
+    case, plan = run
+    L = CL.later_case(*case)
+    settings, route = X.PLANS[plan]
+    eng = X.make_engine(k, DEV, L.base, **settings)
+    route(eng, DEV)
+    V, pos, listed = eng.V, eng.pos.cpu(), L.vertices
+    rows = pos[listed]
+    T, got = CX.table_and_rows(eng, listed)
+    assert torch.equal(got.long(), rows) and T is eng.Zcur
+    steps = rows[1:] - rows[:-1]
+    assert bool((steps > 0).any()) and bool((steps < 0).any())             # the listed rows are not monotone
+    if plan in CL.IN_VERTEX_ORDER:
+        assert torch.equal(rows, listed)
+    else:
+        assert int((rows != listed).sum()) > listed.numel() // 2
+        in_row_order = listed[torch.sort(rows).indices]                    # the list is not in table-row order either
+        assert int((in_row_order != listed).sum()) > listed.numel() // 2
+    pads = int((eng.local.vertex < 0).sum())
+    if plan in CL.THREE_BLOCK_PLANS:
+        assert eng.Zcur.shape[0] == eng.X_loc.shape[0] == V + pads == 702 and pads == 2
+        assert set(_edge_vertices(eng)) <= set(listed.tolist())
+        blocks = X.block_of_vertex(eng)[listed.numpy()]
+        assert set(blocks.tolist()) == {0, 1, 2}
+    else:
+        assert eng.Zcur.shape[0] == V and pads == 0
+    assert eng.Zcur.stride() == (eng.ld, 1) and eng.X_loc.stride() == (eng.ld, 1)
+    if case in CL.PADDED_CASES:
+        assert eng.ld > eng.d and len(eng.tiles) == 2
+    else:
+        assert eng.ld == eng.d                                              # tiles or not
+    # X_loc is in local-row order, which on one GPU is the table-row order: pos-mapped rows ARE its right rows
+    TX, xrows = CX.table_and_rows(eng, listed, "X")
+    assert TX is eng.X_loc and torch.equal(xrows.long(), rows)
+    assert torch.equal(TX[xrows.long(), :eng.d].double(), L.base.X[listed].to(L.dtype).double())
+
+
+def test_edge_vertices_cover_the_plans_of_b(k):
+    """The three-block engines of B (the sequence plans; chunks3_class is covered above): the list holds both neighbours
+    of their block edges too."""
+    listed = set(CL.vertex_list().tolist())
+    for plan, settings in X.SEQUENCE_PLANS.items():
+        eng = X.make_engine(k, DEV, X.sequence_case(), **settings)
+        assert len(eng.blocks) == 3 and set(_edge_vertices(eng)) <= listed, plan
+
+
+@pytest.mark.parametrize("run", [CX.CURRENT_RUNS[0], CX.CURRENT_RUNS[-1]], ids=CX.current_id)
+def test_current_table_passes_through_all_three_tables(k, run):
+    checks = CX.run_current_table(k, DEV, run)
+    assert checks.failed == [] and len(checks.cur_seen) == len(CX.STEPS) and set(checks.cur_seen) == {0, 1, 2}
+    assert not any("knn7" in n or "mixture" in n for n in checks.names)    # the later consumers: HIP kernels only
